@@ -17,8 +17,17 @@ time, exact bf16 re-score of the survivors, the exact kernel 6/8 as a device-gat
 DESIGN §4.10); "exact" runs the one-pass exact scan (kernel 6 at config 3).  Both return the
 oracle's top-k; the roofline is priced on the bytes the timed kernel actually reads.
 
+A plain run sets up, warms up, times the K steps and prints the JSON line (QPS, ms_per_step, the
+roofline from the HIP events inside the timed steps).  --full adds what takes work of its own after
+the timed region: the two-pass scan's survivor statistics (`two_pass`), the oracle check of the last
+timed step (`oracle_check`, --oracle-stride) and the CPU baseline (`cpu_baseline`, --no-cpu-baseline
+leaves it out).  --dump-outputs DIR writes the last timed step's answer (scores.npy f32 [nq][k],
+rows.npy f64 [nq][k]: what a caller of the path receives) after the timed region; corpus and queries
+come from the seeded counter-based generator, so equal arguments give equal inputs in every run.
+
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--nq Q] [--k K] [--dim D]
-                       [--dtype bf16|f16|f32] [--scan auto|exact] [--no-cpu-baseline]
+                       [--dtype bf16|f16|f32] [--scan auto|exact] [--full [--no-cpu-baseline]]
+                       [--dump-outputs DIR]
 """
 import argparse
 import ctypes
@@ -62,8 +71,12 @@ def parse():
                     help="auto: the exact two-pass scan (int8 screen + exact re-score) where it applies")
     ap.add_argument("--allow-host-exchange", action="store_true",
                     help="N > 1: if RCCL cannot be initialised, exchange through host memory instead of failing")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    # oracle check of the last timed step (rank 0; at N > 1 the gathered answer): every `stride`-th
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also: two_pass survivor statistics, oracle check, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's answer as DIR/scores.npy (f32) and DIR/rows.npy (f64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    # --full: oracle check of the last timed step (rank 0; at N > 1 the gathered answer): every `stride`-th
     # query against oracle.search.topk_blocks over ALL rows (after the timed region); 0 = off
     ap.add_argument("--oracle-stride", type=int, default=4)
     # An event record is not free on this GPU (~5 us each, measured: profiles/r04k/): the N > 1 step
@@ -367,6 +380,13 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0 and out is not None:
+        # the last timed step's answer as its caller receives it: scores f32 [nq][k], rows int64 [nq][k]
+        # (stored as f64: exact below 2^53); at N > 1 the gathered merge's, on rank 0
+        import numpy as np
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "scores.npy"), out[0].cpu().numpy().astype(np.float32))
+        np.save(os.path.join(a.dump_outputs, "rows.npy"), out[1].cpu().numpy().astype(np.float64))
 
     def avg(i, j):
         return sum(e[i].elapsed_time(e[j]) for e in evs.values()) / len(evs)
@@ -479,7 +499,7 @@ def main():
         result["roofline"].update({"bound": "mfma", "achieved": round(tflops, 2), "peak": F32_MFMA_PEAK_TFLOPS,
                                    "unit": "TFLOP/s", "frac": round(tflops / F32_MFMA_PEAK_TFLOPS, 4),
                                    "hbm_gbps": round(achieved, 1)})
-    if kern == 10:
+    if a.full and kern == 10:
         # the whole two-pass step's reads: kernel 10's bytes + the select kernel's (candidate lists,
         # the bf16 queries, the survivors' bf16 rows) — what one batch costs in HBM traffic
         diag, fb = ixs[(a.steps - 1) % copies].screen_diag(a.nq, a.k, ws)
@@ -495,7 +515,7 @@ def main():
             "note": "step_bytes = kernel 10's bytes + select (candidate lists, bf16 queries, survivor rows)"}
 
     check_ok = True
-    if rank == 0 and a.oracle_stride > 0 and out is not None:
+    if a.full and rank == 0 and a.oracle_stride > 0 and out is not None:
         if multi:
             # rank 0 holds the gathered answer (global rows) but only its own shard: the oracle reads
             # every shard's rows from the same counter-based generator the ranks built them from
@@ -506,7 +526,7 @@ def main():
         result["oracle_check"] = oracle_check(read, a.rows, q, out, a)
         result["oracle_check"]["answer"] = "gathered merge (rank 0)" if multi else "single shard"
         check_ok = result["oracle_check"]["ok"]
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(ix, q, a)
     if rank == 0:
         print(json.dumps(result), flush=True)

@@ -27,7 +27,7 @@ def _free_port():
 def test_two_rank_bench_step_is_oracle_checked(rows, extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--backend", "gloo", "--one-device", "--check", "--no-cpu-baseline",
+           "--gpus", "2", "--backend", "gloo", "--one-device", "--check", "--full", "--no-cpu-baseline",
            "--rows", str(rows), "--steps", "3", "--warmup", "1"] + extra
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
