@@ -215,7 +215,10 @@ int rfx_index_screen_state(rfx_index_t h, int* out_mode, int64_t* out_bytes, int
  * max quantisation-error norm, max tile scale). */
 int rfx_index_screen_read(rfx_index_t h, int64_t tile0, int64_t ntiles, int8_t* codes_h, float* scales_h,
                           uint32_t* live_h, float* stats_h);
-/* The kernel rfx_search runs for (nq, k): 0 VALU, 1/2/3/6/8/9 exact MFMA scans, 10 the two-pass scan. */
+/* The kernel rfx_search runs for (nq, k): 0 VALU, 1/2/3/6/8/9 exact MFMA scans, 10 the two-pass scan of a
+ * batch (9 or more questions, k <= 10), 11 the two-pass scan of 1..8 questions in one launch: every k in
+ * 1..64, any dtype, dim 768 or 1024, on an index holding the int8 copy.
+ * rfx_search_workspace_bytes(h, nq, k) does not depend on whether the copy exists yet. */
 int rfx_search_plan(rfx_index_t h, int64_t nq, int k, int* out_kernel);
 /* After a two-pass search with workspace ws_d (stream-ordered; this call synchronises): per query
  * {kept screen candidates, survivors re-scored (-1 = sent to the fallback)} into diag_h [nq][2], and

@@ -30,14 +30,42 @@
 // no co-residency of the grid is needed (round 4 withdrew a version that split the search statically
 // over the waiting blocks: two launches on one device could fill every CU with waiting blocks).
 // Algorithmic bytes: N·d codes + ⌈N/32⌉·16 tile records + the re-scored rows (a few per query).
+//
+// Every k in 1..64 (round 7).  The text above speaks of lists of 16 (k <= 16; for k <= 4 the exact fallback
+// runs at its own K slot 4, inside the launch or gated, over cs / cr regions sized for records of 16).  For
+// 17 <= k <= 64 the same kernel is instantiated with lists of KL = 64 (k_screen_valu64.hip): a wave list is
+// one entry per lane and query slot; the block record is its 63 best (A, row) and, in entry 63, its drop
+// bound; cand_x is [nq][blocks][64]; the fallback is the VALU search's K slot 64.  Nothing in the exactness
+// argument depends on the length.  What differs at 64:
+//   * step 3: 256 wave-list entries per block and query — every wave ranks its own 64 of each query;
+//   * early re-score: at most 16 entries per block and query (LB_b - e2 admits >= k entries of every block);
+//     the last block re-scores whatever survivor is left without a key, as ever;
+//   * the last block stages the first SL entries of each record in LDS (SL = 16 / 32 / 64 by the block
+//     count: blocks * SL <= kFusedLdsCand, the LDS of the list-16 form — whole records are 128 KB) and reads
+//     the drop bounds and k-th entries from memory; a record whose staged entries all survive might hold
+//     survivors past them: not proven, the exact search answers.  k = 64 has no k-th record entry (entry 63
+//     is the drop bound), so its bound is the k-th best record head, as k = 16's with lists of 16;
+//   * kSurvCap stays 1024 (survivors come from <= 4096 staged entries; their rank is ns^2 / 256 compares a
+//     thread), the host guard is blocks * 16 <= kFusedLdsCand and blocks <= 256 (one record per thread for
+//     the drop bounds); static LDS ~95 KB at 8 query slots (of 160 KB, one workgroup per CU).
 #include "k_scan_valu.h"
 
 namespace rfx {
 namespace {
 
-constexpr int kK = 16;           // A-list length (k <= 16)
-constexpr int kDropRow = -2;     // record entry 15: the block's drop bound, not a row
-constexpr int kSurvCap = 1024;   // survivors re-scored by the last block; more -> the exact fallback
+// The A-list length KL is a template parameter of the kernel: 16 (k <= 16) or 64 (17 <= k <= 64).  This
+// file compiles one of them (k_screen_valu64.hip includes it with RFX_K11_LIST 64: two translation
+// units, built in parallel).
+#ifndef RFX_K11_LIST
+#define RFX_K11_LIST 16
+#endif
+constexpr int kListTU = RFX_K11_LIST;
+static_assert(kListTU == 16 || kListTU == 64, "list lengths: 16 and 64");
+constexpr int kDropRow = -2;     // the record's last entry: the block's drop bound, not a row
+// survivors re-scored and ranked by the last block; more -> the exact fallback.  Either list length: the
+// survivors come from the staged part of the records (at most kFusedLdsCand entries), a quarter of which
+// ranks in ~4 compares per thread and survivor (16 KB of LDS)
+constexpr int kSurvCap = 1024;
 
 template <int DT>
 __device__ __forceinline__ float qelem(const void* Q, int64_t i) {
@@ -105,12 +133,12 @@ __device__ unsigned long long g_k11_last[8];
 #endif
 
 // The exact fallback inside kernel 11's launch (a lone question): claim virtual blocks of the one-launch
-// VALU search (K slot 16) until all are taken.  Every branch around a barrier here is on a readfirstlane
+// VALU search (K slot KS: the exact plan's, 4 / 16 / 64) until all are taken.  Every branch around a barrier here is on a readfirstlane
 // value (uniform to the compiler): with the claimed unit read as a plain LDS value the compiler structurised
 // the loop as a divergent one — lanes 1-63 of wave 0 went back to the barrier before lane 0 claimed the
 // next unit, and the block re-ran one unit forever (round 5, a 120-s test timeout).  Bounded: a block
 // claims at most gridDim.x units.
-template <int DT, int D, int VPLV>
+template <int DT, int D, int VPLV, int KS>
 __device__ __attribute__((noinline)) void k11_fallback(const void* X, int nrows, const void* Q, int nq, int rows_per_wave,
                                                        float* cand_s, int* cand_r, const uint32_t* mask, uint32_t* vtau,
                                                        uint32_t* vctr, uint32_t* clm, int k_out, float* out_s,
@@ -123,7 +151,7 @@ __device__ __attribute__((noinline)) void k11_fallback(const void* X, int nrows,
     const int u = __builtin_amdgcn_readfirstlane(unit);
     __syncthreads();
     if (u >= (int)gridDim.x) break;
-    scan_valu_body<DT, 1, 16, VPLV, true>((const uint8_t*)X, nrows, D, Q, nq, rows_per_wave, cand_s, cand_r,
+    scan_valu_body<DT, 1, KS, VPLV, true>((const uint8_t*)X, nrows, D, Q, nq, rows_per_wave, cand_s, cand_r,
                                           (int)gridDim.x, mask, vtau, FusedOut{vctr, k_out, out_s, out_r, nullptr}, u,
                                           (int)gridDim.x);
   }
@@ -131,7 +159,7 @@ __device__ __attribute__((noinline)) void k11_fallback(const void* X, int nrows,
 
 constexpr int kKeepChunks = 2;  // the kept-score waves' chunks of 64 rows (KEEP below)
 
-template <int DT, int D, int NQT, bool KEEP>
+template <int DT, int D, int NQT, bool KEEP, int KL, int KS>
 __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restrict__ X8, const uint4* __restrict__ tmeta,
                                                           const uint32_t* __restrict__ stats, int nrows,
                                                           const void* __restrict__ X, const void* __restrict__ Q, int nq,
@@ -142,6 +170,7 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
                                                           int64_t* __restrict__ out_r, int force,
                                                           uint32_t* __restrict__ vtau, uint32_t* __restrict__ vctr) {
   constexpr int C = D / 256;
+  constexpr int kK = KL;  // A-list length: wave lists, block records ([kK - 1] rows + the drop bound), cand_x
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, j = lane & 15;
   const int n_lists = gridDim.x;
   // state (per index and stream): [0] the arrival counter (zero on entry, left zero), [24] the
@@ -161,12 +190,12 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
   constexpr int VPR0 = D * ESZV / 16;
   constexpr int VPLV = (VPR0 + 15) / 16 <= 4 ? 4 : (VPR0 + 15) / 16 <= 8 ? 8 : (VPR0 + 15) / 16 <= 12 ? 12 : 16;
   constexpr bool INL = screen_valu_inline_fallback(NQT, DT, D);
-  // the exact fallback: claim virtual blocks of the one-launch VALU search (K slot 16) until all are taken
+  // the exact fallback: claim virtual blocks of the one-launch VALU search (K slot KS) until all are taken
   // (a call, not inlined: the fallback's registers stay out of the screen's allocation — inlined, kernel 11
   // went from 256 to 256 + 57 AGPR registers and its screen from 41.6 to 49.8 us at config 2, round 5)
   auto fallback = [&]() {
     if constexpr (INL)
-      k11_fallback<DT, D, VPLV>(X, nrows, Q, nq, rows_per_wave, cand_s, cand_r, mask, vtau, vctr, clm, k_out, out_s,
+      k11_fallback<DT, D, VPLV, KS>(X, nrows, Q, nq, rows_per_wave, cand_s, cand_r, mask, vtau, vctr, clm, k_out, out_s,
                                 out_r);
   };
   RFX_K11_T(0);
@@ -496,6 +525,70 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
     d = wave_max_f32(d);
     if (lane == 0) wdm[w][qi] = d;
   }
+  if constexpr (kK == 64) {
+    // A list of 64: the block's 256 entries, 64 per wave.  Wave w ranks ITS list's entries of every query
+    // against all 256 (the ranks of 256 entries by one wave were 4x the compares on one query's critical
+    // path), stores those that rank below 63 into the record and, in LDS, the record's scores and rows in
+    // rank order; after a barrier the query's wave (w, w + 4) writes the empty tail and the drop bound and
+    // picks the entries re-scored early.
+    __shared__ float srt[NQT][kK];
+    __shared__ float pd[4][NQT];
+    __shared__ int pnv[4][NQT];
+    __shared__ uint32_t plb[NQT];
+    if (tid < NQT) plb[tid] = 0u;
+    __syncthreads();
+    for (int qi = 0; qi < nq; ++qi) {
+      const uint64_t mine = mk[qi][w * kK + lane];
+      int rank = 0;
+#pragma unroll 16
+      for (int i = 0; i < 4 * kK; ++i) rank += mk[qi][i] > mine ? 1 : 0;
+      const bool v = mine != 0ull;
+      const float ms_ = unord_f32((uint32_t)(mine >> 32));
+      float d = v && rank >= kK - 1 ? ms_ : -__builtin_inff();  // past the record's 63 entries: dropped
+      d = wave_max_f32(d);
+      const int nv = (int)__popcll(__ballot(v));
+      if (lane == 0) {
+        pd[w][qi] = d;
+        pnv[w][qi] = nv;
+      }
+      const int64_t o0 = ((int64_t)qi * n_lists + blockIdx.x) * kK;
+      if (v && rank < kK - 1) {
+        __hip_atomic_store((uint32_t*)cand_s + o0 + rank, __float_as_uint(ms_), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(cand_r + o0 + rank, (int)(~(uint32_t)mine), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(cand_x + o0 + rank, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        srt[qi][rank] = ms_;
+        xrow[qi][rank] = (int)(~(uint32_t)mine);
+      }
+      // the block's k-th best A (LB_b below); distinct (score, row) keys: one lane of the block holds it
+      if (v && rank == k_out - 1) plb[qi] = ord_f32(ms_);
+    }
+    __syncthreads();
+    for (int qi = w; qi < nq; qi += 4) {
+      const int nv = min(pnv[0][qi] + pnv[1][qi] + pnv[2][qi] + pnv[3][qi], kK - 1);  // record entries
+      const float d = fmaxf(fmaxf(fmaxf(wdm[0][qi], wdm[1][qi]), fmaxf(wdm[2][qi], wdm[3][qi])),
+                            fmaxf(fmaxf(pd[0][qi], pd[1][qi]), fmaxf(pd[2][qi], pd[3][qi])));
+      const int64_t o0 = ((int64_t)qi * n_lists + blockIdx.x) * kK;
+      if (lane >= nv && lane < kK - 1) {  // empty tail of the record
+        __hip_atomic_store((uint32_t*)cand_s + o0 + lane, __float_as_uint(-__builtin_inff()), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(cand_r + o0 + lane, kEmptyRow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(cand_x + o0 + lane, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      if (lane == kK - 1) {
+        __hip_atomic_store((uint32_t*)cand_s + o0 + lane, __float_as_uint(d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(cand_r + o0 + lane, kDropRow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+      // Early re-score as for a list of 16 (below): the entries at or above LB_b - e2, a prefix of the ranks.
+      // At most kEarly64 of them per query: LB_b - e2 admits at least k entries of every block, far more than a
+      // block holds of the answer, and whatever is left without a key the last block re-scores itself.
+      constexpr int kEarly64 = 16;
+      const uint32_t lbb = plb[qi];
+      const float cutb = lbb ? unord_f32(lbb) - e2_lds[qi] : -__builtin_inff();
+      const bool rx = lane < nv && lane < kEarly64 && srt[qi][lane < nv ? lane : 0] >= cutb;
+      const int nx = (int)__popcll(__ballot(rx));
+      if (lane == 0) nxl[qi] = nx;
+    }
+  } else {
   __syncthreads();
   for (int qi = w; qi < nq; qi += 4) {
     const uint64_t mine = mk[qi][lane];
@@ -541,6 +634,7 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
     const int nx = (int)__popcll(__ballot(rx));
     if (lane == 0) nxl[qi] = nx;
   }
+  }  // (kK == 16)
   // the early re-score (a block that is not the last, after it arrived): the entries above, 16 lanes each
   // (the last block's layout), all queries' entries in a row
   auto early_rescore = [&]() {
@@ -633,7 +727,15 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
     }
     return;
   }
-  const int n = n_lists * kK;  // <= kFusedLdsCand (host check)
+  const int n = n_lists * kK;  // kK == 16: <= kFusedLdsCand (host check)
+  // A list of 64: the records' first SL entries are staged (16 with more than 128 blocks, 32 with more than
+  // 64, else whole records; n_lists * SL <= kFusedLdsCand, host check) — whole records would take 128 KB of
+  // LDS.  A record whose staged entries all survive may hold survivors past them: not proven (survivors()
+  // below).  Its drop bound and k-th entry are read from memory.  Staged index i = record * SL + entry.
+  const int slsh = kK == 16 ? 4 : n_lists > 128 ? 4 : n_lists > 64 ? 5 : 6;
+  const int SL = 1 << slsh;
+  const int nst = kK == 16 ? n : n_lists * SL;  // staged entries
+  auto gidx = [&](int i) { return kK == 16 ? i : ((i >> slsh) * kK + (i & (SL - 1))); };  // index in the records
   __shared__ float bs[kFusedLdsCand];
   __shared__ int br[kFusedLdsCand];
   __shared__ int sv[kSurvCap];    // survivor -> record index
@@ -653,13 +755,26 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
     // (16 per thread: config 2's 250 records of 16 in one round trip; the loads are unconditional, on a
     // clamped index, so no branch and no drain sits between them)
     constexpr int UL = 16;
-    for (int base = 0; base < n; base += 256 * UL) {
+    // a list of 64: each record's drop bound (its last entry, always) and k-th entry, from memory (one record
+    // per thread: n_lists <= 256), requested with the first round of the copy
+    float dmax = -__builtin_inff();
+    uint32_t gk = 0u;  // the largest block bound LB_b (record entry k - 1; k <= kK - 1)
+    uint32_t d64 = 0u, s64 = 0u;
+    int r64 = kEmptyRow;
+    if constexpr (kK == 64) {
+      const int c = tid < n_lists ? tid : n_lists - 1;
+      const int64_t o = (int64_t)qi * n + (int64_t)c * kK;
+      d64 = __hip_atomic_load((const uint32_t*)cand_s + o + kK - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      s64 = __hip_atomic_load((const uint32_t*)cand_s + o + k_out - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      r64 = __hip_atomic_load(cand_r + o + k_out - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    for (int base = 0; base < nst; base += 256 * UL) {
       uint32_t sv8[UL];
       int rv8[UL];
 #pragma unroll
       for (int u = 0; u < UL; ++u) {
         const int i = base + u * 256 + tid;
-        const int ic = i < n ? i : n - 1;
+        const int ic = gidx(i < nst ? i : nst - 1);
         sv8[u] = __hip_atomic_load((const uint32_t*)cand_s + (int64_t)qi * n + ic, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
         rv8[u] = __hip_atomic_load(cand_r + (int64_t)qi * n + ic, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -667,10 +782,16 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
 #pragma unroll
       for (int u = 0; u < UL; ++u) {
         const int i = base + u * 256 + tid;
-        if (i < n) {
+        if (i < nst) {
           bs[i] = __uint_as_float(sv8[u]);
           br[i] = rv8[u];
         }
+      }
+    }
+    if constexpr (kK == 64) {
+      if (tid < n_lists) {
+        dmax = __uint_as_float(d64);
+        if (k_out < kK && r64 != kEmptyRow && r64 != kDropRow) gk = ord_f32(__uint_as_float(s64));
       }
     }
     if (tid == 0) {
@@ -684,13 +805,13 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
     // records are few) — distinct live rows either way.  Each wave extracts the k best of its 256 keys
     // (4 per lane, sorted in registers) by k rounds of a wave max; wave 0 ranks the 4k finalists (the
     // union of the waves' top-k holds the top-k values with their multiplicity).
-    float dmax = -__builtin_inff();
-    uint32_t gk = 0u;  // the largest block bound LB_b (record entry k - 1; k <= 15)
-    for (int c = tid; c < n_lists; c += 256) {
-      const int i = c * kK + kK - 1;
-      if (br[i] == kDropRow) dmax = fmaxf(dmax, bs[i]);
-      const int i2 = c * kK + k_out - 1, r2 = br[i2];
-      if (k_out < kK && r2 != kEmptyRow && r2 != kDropRow) gk = max(gk, ord_f32(bs[i2]));
+    if constexpr (kK == 16) {
+      for (int c = tid; c < n_lists; c += 256) {
+        const int i = c * kK + kK - 1;
+        if (br[i] == kDropRow) dmax = fmaxf(dmax, bs[i]);
+        const int i2 = c * kK + k_out - 1, r2 = br[i2];
+        if (k_out < kK && r2 != kEmptyRow && r2 != kDropRow) gk = max(gk, ord_f32(bs[i2]));
+      }
     }
     dmax = wave_max_f32(dmax);
     gk = wave_max_u32(gk);
@@ -698,8 +819,8 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
       red[w] = dmax;
       redg[w] = gk;
     }
-    const bool every = n <= 1024;
-    const int m = (force & 32) ? 0 : every ? n : n_lists;  // <= 1024
+    const bool every = nst <= 1024;
+    const int m = (force & 32) ? 0 : every ? nst : n_lists;  // <= 1024
     uint32_t a0, a1, a2, a3;  // this lane's keys, sorted
     {
       uint32_t ak[4];
@@ -708,7 +829,7 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
         const int c = w * 256 + u * 64 + lane;
         uint32_t key = 0u;
         if (c < m) {
-          const int i = every ? c : c * kK;
+          const int i = every ? c : c << slsh;
           const int r = br[i];
           key = r != kEmptyRow && r != kDropRow ? ord_f32(bs[i]) : 0u;
         }
@@ -753,6 +874,17 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
           v = cnt >= k_out ? c1 : v;
         }
         lb = v;
+      } else if constexpr (kK == 64) {
+        // 4 kK = 256 finalists, four per lane: their k-th largest with multiplicity, the same bitwise search
+        const uint32_t f0 = fin[lane], f1 = fin[64 + lane], f2 = fin[128 + lane], f3 = fin[192 + lane];
+        uint32_t v = 0u;
+        for (int bit = 31; bit >= 0; --bit) {
+          const uint32_t c1 = v | (1u << bit);
+          const int cnt = (int)(__popcll(__ballot(f0 >= c1)) + __popcll(__ballot(f1 >= c1)) +
+                                __popcll(__ballot(f2 >= c1)) + __popcll(__ballot(f3 >= c1)));
+          v = cnt >= k_out ? c1 : v;
+        }
+        lb = v;
       } else {
         const uint32_t x = fin[lane];  // 4 kK = 64 finalists, one per lane
         int ge = 0, gt = 0;
@@ -778,13 +910,17 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
     // survivors: the entries at or above the cut; a record is sorted best first, so its scan ends at
     // the first entry below the cut (most records: at their best entry)
     for (int c = tid; c < n_lists; c += 256) {
-      const int i0 = c * kK;
-      for (int e = 0; e < kK - 1; ++e) {
+      const int i0 = c << slsh;
+      const int emax = SL < kK - 1 ? SL : kK - 1;
+      int e = 0;
+      for (; e < emax; ++e) {
         const int r = br[i0 + e];
         if (r == kEmptyRow || !(bs[i0 + e] >= cut)) break;
         const int j2 = atomicAdd(&n_sv, 1);
         if (j2 < kSurvCap) sv[j2] = i0 + e;
       }
+      // (a list of 64) every staged entry of this record survives: the entries after them might
+      if (e == emax && emax < kK - 1) fail = 1;
     }
     __syncthreads();
     if (n_sv > kSurvCap && tid == 0) fail = 1;
@@ -797,7 +933,8 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
       // write them; a key still 0 (this block's own entries, a block not done yet) is re-scored here
       for (int e = tid; e < ns; e += 256) {
         const int i = sv[e];
-        const uint32_t x = __hip_atomic_load(cand_x + (int64_t)qi * n + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t x =
+            __hip_atomic_load(cand_x + (int64_t)qi * n + gidx(i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (x)
           skey[e] = ((uint64_t)x << 32) | (uint32_t)(~(uint32_t)br[i]);
         else
@@ -886,65 +1023,93 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
 
 }  // namespace
 
+#if RFX_K11_LIST == 16
 #ifdef RFX_DEBUG_BUILD
 int dbg_k11_times(unsigned long long* blocks_h, unsigned long long* last_h) {
   if (hipMemcpyFromSymbol(blocks_h, HIP_SYMBOL(g_k11_t), sizeof(g_k11_t)) != hipSuccess) return -1;
   return hipMemcpyFromSymbol(last_h, HIP_SYMBOL(g_k11_last), sizeof(g_k11_last)) == hipSuccess ? 0 : -1;
 }
 #endif
+#endif
 
-// One launch: grid (blocks) × 256 threads, one query slice of up to 8 queries.  The in-launch fallback
-// (a lone question) is the one-launch VALU search's K slot 16 over the same plan (k 5..16; its state
+// One launch: grid (blocks) × 256 threads, one query slice of up to 8 queries, lists of kListTU (this
+// translation unit's length).  The in-launch fallback (a lone question) is the one-launch VALU search at the
+// exact plan's K slot over the same plan: 4 (k <= 4) or 16 with lists of 16, 64 with lists of 64 (its state
 // vstate: bounds, then counters).
-int launch_screen_valu(const ValuPlan& p, const int8_t* X8, const void* tmeta, const uint32_t* stats, int nrows, int D,
-                       int dtype, const void* X, const void* Q, int nq, const uint32_t* mask, uint32_t* state,
-                       uint32_t* vstate, float* cs, int* cr, uint32_t* cx, int k, float* out_s, int64_t* out_r,
-                       int force, hipStream_t st) {
+#if RFX_K11_LIST == 16
+#define RFX_K11_LAUNCH launch_screen_valu16
+#else
+#define RFX_K11_LAUNCH launch_screen_valu64
+#endif
+int launch_screen_valu16(const ValuPlan& p, const int8_t* X8, const void* tmeta, const uint32_t* stats, int nrows, int D,
+                         int dtype, const void* X, const void* Q, int nq, const uint32_t* mask, uint32_t* state,
+                         uint32_t* vstate, float* cs, int* cr, uint32_t* cx, int k, float* out_s, int64_t* out_r,
+                         int force, hipStream_t st);
+int launch_screen_valu64(const ValuPlan& p, const int8_t* X8, const void* tmeta, const uint32_t* stats, int nrows, int D,
+                         int dtype, const void* X, const void* Q, int nq, const uint32_t* mask, uint32_t* state,
+                         uint32_t* vstate, float* cs, int* cr, uint32_t* cx, int k, float* out_s, int64_t* out_r,
+                         int force, hipStream_t st);
+
+int RFX_K11_LAUNCH(const ValuPlan& p, const int8_t* X8, const void* tmeta, const uint32_t* stats, int nrows, int D,
+                   int dtype, const void* X, const void* Q, int nq, const uint32_t* mask, uint32_t* state,
+                   uint32_t* vstate, float* cs, int* cr, uint32_t* cx, int k, float* out_s, int64_t* out_r, int force,
+                   hipStream_t st) {
+  constexpr int kK = kListTU;
   if (!cx) return -1;
   if (nq < 1 || nq > 8 || k < 1 || k > kK || (D != 768 && D != 1024)) return -1;
-  if ((int64_t)p.blocks * kK > (int64_t)1 << 30) return -1;
-  if (screen_valu_inline_fallback(nq == 1 ? 1 : 8, dtype, D) && (!vstate || p.q_slices != 1 || valu_k_slot(k) != 16))
-    return -1;
+  if (screen_valu_list(k) != kK || p.k_slot != valu_k_slot(k)) return -1;
+  // the last block stages 16 entries of every record in LDS (whole records with lists of 16)
+  if ((int64_t)p.blocks * 16 > kFusedLdsCand) return -1;
+  if (kK == 64 && p.blocks > 256) return -1;  // (one record per thread: the drop bounds)
+  if (screen_valu_inline_fallback(nq == 1 ? 1 : 8, dtype, D) && (!vstate || p.q_slices != 1)) return -1;
   const dim3 grid((unsigned)p.blocks);
   uint32_t* const vtau = vstate;
   uint32_t* const vctr = vstate ? vstate + kValuFusedMaxNq : nullptr;
   // the kept-score waves (KEEP) when every wave streams at most kKeepChunks 64-row chunks
   const bool keep = p.rows_per_wave <= 64 * kKeepChunks;
-#define RFX_SV(DTV, DV, NQ)                                                                                         \
-  do {                                                                                                              \
-    if (keep)                                                                                                       \
-      hipLaunchKernelGGL((screen_valu_kernel<DTV, DV, NQ, true>), grid, dim3(256), 0, st, X8, (const uint4*)tmeta,    \
-                         stats, nrows, X, Q, nq, p.rows_per_wave, mask, state, cs, cr, cx, k, out_s, out_r, force,    \
-                         vtau, vctr);                                                                               \
-    else                                                                                                            \
-      hipLaunchKernelGGL((screen_valu_kernel<DTV, DV, NQ, false>), grid, dim3(256), 0, st, X8, (const uint4*)tmeta,   \
-                         stats, nrows, X, Q, nq, p.rows_per_wave, mask, state, cs, cr, cx, k, out_s, out_r, force,    \
-                         vtau, vctr);                                                                               \
+  // a lone question at k <= 4: the in-launch fallback at the exact plan's K slot 4
+  constexpr int kSlot4 = kK == 16 ? 4 : kK;
+  const bool slot4 = kK == 16 && nq == 1 && p.k_slot == 4 && screen_valu_inline_fallback(1, dtype, D);
+#define RFX_SV(DTV, DV, NQ, KSV)                                                                                     \
+  do {                                                                                                               \
+    if (keep)                                                                                                        \
+      hipLaunchKernelGGL((screen_valu_kernel<DTV, DV, NQ, true, kK, KSV>), grid, dim3(256), 0, st, X8,                 \
+                         (const uint4*)tmeta, stats, nrows, X, Q, nq, p.rows_per_wave, mask, state, cs, cr, cx, k,     \
+                         out_s, out_r, force, vtau, vctr);                                                           \
+    else                                                                                                             \
+      hipLaunchKernelGGL((screen_valu_kernel<DTV, DV, NQ, false, kK, KSV>), grid, dim3(256), 0, st, X8,                \
+                         (const uint4*)tmeta, stats, nrows, X, Q, nq, p.rows_per_wave, mask, state, cs, cr, cx, k,     \
+                         out_s, out_r, force, vtau, vctr);                                                           \
   } while (0)
   // (2 and 4 query slots for the kept-score waves: a batch of 2 paid the stream work of 8 slots — 32 of its
   // 54 us, profiles/r06/k11_nq8_ablate/; the list path keeps 1 or 8)
-#define RFX_SV_KEEP(DTV, DV, NQ)                                                                                  \
-  hipLaunchKernelGGL((screen_valu_kernel<DTV, DV, NQ, true>), grid, dim3(256), 0, st, X8, (const uint4*)tmeta, stats, \
-                     nrows, X, Q, nq, p.rows_per_wave, mask, state, cs, cr, cx, k, out_s, out_r, force, vtau, vctr)
+#define RFX_SV_KEEP(DTV, DV, NQ)                                                                                   \
+  hipLaunchKernelGGL((screen_valu_kernel<DTV, DV, NQ, true, kK, kK>), grid, dim3(256), 0, st, X8, (const uint4*)tmeta, \
+                     stats, nrows, X, Q, nq, p.rows_per_wave, mask, state, cs, cr, cx, k, out_s, out_r, force, vtau,   \
+                     vctr)
 #define RFX_SV_D(DTV)                            \
   if (D == 768) {                                \
-    if (nq == 1)                                 \
-      RFX_SV(DTV, 768, 1);                       \
+    if (nq == 1 && slot4)                        \
+      RFX_SV(DTV, 768, 1, kSlot4);               \
+    else if (nq == 1)                            \
+      RFX_SV(DTV, 768, 1, kK);                   \
     else if (keep && nq <= 2)                    \
       RFX_SV_KEEP(DTV, 768, 2);                  \
     else if (keep && nq <= 4)                    \
       RFX_SV_KEEP(DTV, 768, 4);                  \
     else                                         \
-      RFX_SV(DTV, 768, 8);                       \
+      RFX_SV(DTV, 768, 8, kK);                   \
   } else {                                       \
-    if (nq == 1)                                 \
-      RFX_SV(DTV, 1024, 1);                      \
+    if (nq == 1 && slot4)                        \
+      RFX_SV(DTV, 1024, 1, kSlot4);              \
+    else if (nq == 1)                            \
+      RFX_SV(DTV, 1024, 1, kK);                  \
     else if (keep && nq <= 2)                    \
       RFX_SV_KEEP(DTV, 1024, 2);                 \
     else if (keep && nq <= 4)                    \
       RFX_SV_KEEP(DTV, 1024, 4);                 \
     else                                         \
-      RFX_SV(DTV, 1024, 8);                      \
+      RFX_SV(DTV, 1024, 8, kK);                  \
   }
   if (dtype == RFX_F32) {
     RFX_SV_D(RFX_F32)
@@ -958,5 +1123,18 @@ int launch_screen_valu(const ValuPlan& p, const int8_t* X8, const void* tmeta, c
 #undef RFX_SV
   return 0;
 }
+#undef RFX_K11_LAUNCH
+
+#if RFX_K11_LIST == 16
+int launch_screen_valu(const ValuPlan& p, const int8_t* X8, const void* tmeta, const uint32_t* stats, int nrows, int D,
+                       int dtype, const void* X, const void* Q, int nq, const uint32_t* mask, uint32_t* state,
+                       uint32_t* vstate, float* cs, int* cr, uint32_t* cx, int k, float* out_s, int64_t* out_r,
+                       int force, hipStream_t st) {
+  if (k < 1 || k > 64) return -1;
+  return (screen_valu_list(k) == 16 ? launch_screen_valu16 : launch_screen_valu64)(
+      p, X8, tmeta, stats, nrows, D, dtype, X, Q, nq, mask, state, vstate, cs, cr, cx, k, out_s, out_r, force, st);
+}
+#endif
 
 }  // namespace rfx
+

@@ -427,7 +427,7 @@ struct SearchLayout {
   // records / row-offset output they go here first and one pack launch converts them (sharded stores)
   size_t pk_off, pk_r_off;
   // kernel 11 (nq <= 8 on a VALU plan): the exact score keys of the record entries its blocks re-score
-  // before they arrive ([nq][blocks][16] u32, beside the records at cs_off / cr_off)
+  // before they arrive ([nq][blocks][list] u32, list = 16 or 64: beside the records at cs_off / cr_off)
   size_t cx_off;
 };
 
@@ -500,9 +500,16 @@ int make_layout(const Index& ix, int64_t nq, int k, SearchLayout& L, bool search
   if (ix.rows == 0) L.n_cand = 0;
   L.q_off = 0;
   L.tau_off = align_up(L.q_bytes);
+  // Kernel 11's block records share cs / cr with the exact VALU plan's candidates and hold
+  // screen_valu_list(k) entries a block: 16 where the exact plan's K slot is 4 (k <= 4), else the slot's
+  // length.  Sized for the longer of the two whether or not the index holds an int8 copy yet (a workspace
+  // sized before enable_screen fits); the exact plan and its n_cand are unchanged.
+  int64_t rec_cand = L.n_cand;
+  if (search && L.kernel == 0 && nq >= 1 && nq <= 8 && ix.rows > 0)
+    rec_cand = (int64_t)L.vp.n_lists * std::max(L.vp.k_slot, rfx::screen_valu_list(k));
   L.cs_off = L.tau_off + align_up(tau_bytes);
-  L.cr_off = L.cs_off + align_up((size_t)nq * L.n_cand * 4);
-  L.total = L.cr_off + align_up((size_t)nq * L.n_cand * 4);
+  L.cr_off = L.cs_off + align_up((size_t)nq * rec_cand * 4);
+  L.total = L.cr_off + align_up((size_t)nq * rec_cand * 4);
   L.fbk = 0;
   if (search && ix.screen && ix.rows > 0 && (L.kernel == 6 || L.kernel == 8 || L.kernel == 9)) {
     L.sp = rfx::plan_scan_screen(ix.rows, ix.dim, ix.dtype, nq, k, scan_blocks);
@@ -535,7 +542,7 @@ int make_layout(const Index& ix, int64_t nq, int k, SearchLayout& L, bool search
   if (search && L.kernel == 0 && nq >= 1 && nq <= 8 && ix.rows > 0) {
     // (whether or not the index holds an int8 copy yet: a workspace sized before enable_screen fits)
     L.cx_off = L.total;
-    L.total = L.cx_off + align_up((size_t)nq * L.n_cand * 4);
+    L.total = L.cx_off + align_up((size_t)nq * rec_cand * 4);
   }
   return RFX_OK;
 }
@@ -705,8 +712,8 @@ int k11_ablate() {
   return v;
 }
 
-// Kernel 11 (k_screen_valu.hip): a few questions (nq <= 8) on an index holding the int8 copy, on a
-// VALU plan with lists of 16 (5 <= k <= 16) — one launch, plus the gated exact one-launch search.
+// Kernel 11 (k_screen_valu.hip): nq <= 8 questions on an index holding the int8 copy, on a VALU plan, any
+// k in 1..64 (lists of 16 for k <= 16, of 64 above) — one launch, plus the gated exact one-launch search.
 // Kernel-11 launches of one device run one at a time once more than one stream issues them: each then
 // waits for the device's previous one (an event) when that one went to another stream.  Kernel 11 holds
 // one workgroup per CU and its early blocks wait (bounded) for the last one's verdict; two such launches
@@ -738,8 +745,8 @@ bool k11_unordered() {
 }
 
 bool screen_valu_eligible(const Index& ix, const SearchLayout& L, int64_t nq, int k) {
-  return ix.screen && ix.rows > 0 && L.kernel == 0 && L.cx_off && nq >= 1 && nq <= 8 && k <= 16 && L.vp.k_slot == 16 &&
-         rfx::screen_supported(ix.dim, ix.dtype) && fused_enabled();
+  return ix.screen && ix.rows > 0 && L.kernel == 0 && L.cx_off && nq >= 1 && nq <= 8 && k >= 1 && k <= 64 &&
+         L.vp.k_slot == rfx::valu_k_slot(k) && rfx::screen_supported(ix.dim, ix.dtype) && fused_enabled();
 }
 
 }  // namespace

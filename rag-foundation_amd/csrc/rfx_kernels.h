@@ -57,8 +57,11 @@ int launch_search_valu_fused(const ValuPlan& p, const void* X, int nrows, int D,
 // index's int8 copy (codes X8, tile records tmeta, quantiser stats), the exact rows X / queries Q in
 // the index dtype; writes (out_s, out_r) and the fallback gate state[24] (state = the index's
 // per-stream search state + kScreenValuState, zero on entry and left zero except the gate and the
-// launch generation / verdict / claim words).  cx: [nq][blocks][16] u32 workspace, the exact score keys
-// of the record entries (cs / cr) the blocks re-score.  For a lone question (screen_valu_inline_fallback) the
+// launch generation / verdict / claim words).  Any k in 1..64: the wave lists and block records hold
+// screen_valu_list(k) entries (16, or 64 for k >= 17; k_screen_valu.hip / k_screen_valu64.hip), and p is
+// the exact plan of that k (its K slot 4 / 16 / 64 is the fallback's).  cs / cr: the records,
+// [nq][blocks][list] (and the fallback's candidates, [nq][blocks][K slot]); cx: [nq][blocks][list] u32
+// workspace, the exact score keys of the record entries the blocks re-score.  For a lone question (screen_valu_inline_fallback) the
 // exact fallback runs INSIDE the launch when the screen cannot prove its answer (vstate = the
 // one-launch VALU search's state, the per-stream search state's base); otherwise the caller launches
 // the gated one-launch VALU search after it (launch_search_valu_fused with gate = state + 24).
@@ -66,6 +69,7 @@ int launch_screen_valu(const ValuPlan& p, const int8_t* X8, const void* tmeta, c
                        int dtype, const void* X, const void* Q, int nq, const uint32_t* mask, uint32_t* state,
                        uint32_t* vstate, float* cs, int* cr, uint32_t* cx, int k, float* out_s, int64_t* out_r,
                        int force, hipStream_t st);
+constexpr int screen_valu_list(int k) { return k <= 16 ? 16 : 64; }
 constexpr bool screen_valu_inline_fallback(int nqt, int dtype, int D) {
   return nqt == 1 && !(dtype == RFX_F32 && D == 1024);  // (f32 at d 1024: the two bodies together spill)
 }
