@@ -157,6 +157,33 @@ int rfx_search_masked(rfx_index_t h, const void* queries_d, int64_t nq, int k, c
 int rfx_scan_topk_masked(rfx_index_t h, const void* queries_d, int64_t nq, int k,
                          const uint32_t* row_mask_d, int64_t mask_words, float* cand_scores_d,
                          int32_t* cand_rows_d, void* ws_d, size_t ws_bytes, void* stream);
+/* Segmented search: ONE launch for a batch of questions under DIFFERENT metadata filters, reading only
+ * the rows each filter selects (rfx_search_masked applies one mask to all its queries and reads the whole
+ * corpus).  Replaces the same metadata_filter of ask_stream (gemini_rag.py:463-469, allow-listed per
+ * tenant / user at chat.py:295-335) for the case the reference's callers generate: concurrent questions
+ * of several tenants against one store.
+ * n_groups filters.  Group g owns queries [group_q_h[g], group_q_h[g+1]) (the caller sorts queries by group)
+ * and ranges ranges_h[2*i], ranges_h[2*i+1] = {first, count} for i in [group_r_h[g], group_r_h[g+1]):
+ * ascending, disjoint, count > 0, inside [0, rows).  A group with no range answers padding.
+ * Same score rule and order as every rfx_search* (fl32 of the f64 dot; score desc, row asc); tombstoned rows
+ * never rank; k in 1..64; nq <= 1024.  RFX_EINVAL before anything is enqueued for unsorted, overlapping or
+ * out-of-bounds ranges, count <= 0, non-monotone group arrays, group_q_h[n_groups] != nq, k or nq out of range.
+ * The host arrays may be freed on return: the tables go to the front of ws_d through a pinned staging
+ * buffer the index owns (stream-ordered copy).  ws_d: rfx_search_segmented_workspace_bytes(h, nq, k,
+ * n_ranges = group_r_h[n_groups]). */
+int rfx_search_segmented_workspace_bytes(rfx_index_t h, int64_t nq, int k, int64_t n_ranges, size_t* out_bytes);
+int rfx_search_segmented(rfx_index_t h, const void* queries_d, int64_t nq, int k, int n_groups,
+                         const int64_t* group_q_h, const int64_t* group_r_h, const int64_t* ranges_h,
+                         float* out_scores_d, int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream);
+/* Host only (no device call): the work list rfx_search_segmented would run, heaviest items first.  A work
+ * item = up to 8 queries of one group x one chunk of the group's selected rows (its ranges laid end to end;
+ * a chunk may span several); a group is cut into at most 64 chunks of max(128, ceil(rows_g / 64)) rows
+ * rounded up to 64.  items_h (may be NULL with cap 0: count only) receives the first cap items;
+ * *out_lists_per_query = the candidate lists per query (the most chunks of any group, 1..64). */
+int rfx_segmented_plan(int64_t rows, int dim, int dtype, int64_t nq, int k, int n_groups, const int64_t* group_q_h,
+                       const int64_t* group_r_h, const int64_t* ranges_h, int64_t* items_h /* [cap][4]: group,
+                       first query, first selected-row position, selected rows */, int64_t cap, int64_t* out_n_items,
+                       int* out_lists_per_query);
 /* Merge per-query candidate lists into the final top-k.  rows are int32 (rows_are_i64 = 0) or
  * int64 (1); row_offset is added to every returned row (shard base for multi-GPU). */
 int rfx_topk_merge(const float* cand_scores_d, const void* cand_rows_d, int rows_are_i64,

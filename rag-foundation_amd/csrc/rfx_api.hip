@@ -182,6 +182,12 @@ struct Index {
   // launch); keyed by stream so concurrent searches on different streams never share it
   std::mutex state_mu;
   std::map<hipStream_t, uint32_t*> fused_state;
+  // pinned staging of the segmented search's tables (rfx_search_segmented), guarded by seg_mu; seg_ev
+  // marks the end of the last copy out of it
+  void* seg_stage = nullptr;
+  size_t seg_stage_bytes = 0;
+  hipEvent_t seg_ev = nullptr;
+  std::mutex seg_mu;
   // int8 copy of the store for the exact two-pass scan (k_screen.hip): codes
   // [scap][dim], per 32-row tile a 16-B record (scale, live word), and stats[3] (max row norm, max
   // quantisation-error norm, max tile scale; f32 bits).  screen: 0 off, 1 on, 2 on with every batch sent to the
@@ -826,6 +832,16 @@ int rfx_index_destroy(rfx_index_t h) {
   }
   for (auto& kv : ix->fused_state) RFX_HIP(hipFree(kv.second));
   ix->fused_state.clear();
+  if (ix->seg_ev) {
+    RFX_HIP(hipEventSynchronize(ix->seg_ev));
+    RFX_HIP(hipEventDestroy(ix->seg_ev));
+    ix->seg_ev = nullptr;
+  }
+  if (ix->seg_stage) {
+    RFX_HIP(hipHostFree(ix->seg_stage));
+    ix->seg_stage = nullptr;
+    ix->seg_stage_bytes = 0;
+  }
   screen_free(*ix);
   return RFX_OK;
 }
@@ -2140,6 +2156,126 @@ int rfx_synth_rows(uint64_t seed, int64_t row0, int64_t n, int dim, int dtype, v
   if (n == 0) return RFX_OK;
   if (!out_d) return fail(RFX_EINVAL, "null output");
   rfx::launch_synth_rows(seed, row0, n, dim, dtype, out_d, (hipStream_t)stream);
+  RFX_HIP(hipGetLastError());
+  return RFX_OK;
+}
+
+}  // extern "C"
+
+// ---- segmented search: questions under different metadata filters in one launch ---------------------------
+// (the file-search tool's metadata_filter, gemini_rag.py:463-469, allow-listed per tenant / user at
+// chat.py:295-335; kernel: k_scan_seg.h, work list: seg_plan.h)
+namespace {
+struct SegLayout {
+  size_t ranges_off, cs_off, cr_off, total;  // the item table sits at offset 0
+};
+// Sized for the most work items nq queries can have, so the size depends on (nq, k, n_ranges) alone.
+SegLayout seg_layout(int64_t nq, int k, int64_t n_ranges) {
+  SegLayout L;
+  L.ranges_off = align_up((size_t)rfx::seg_max_items(nq) * sizeof(rfx::SegItemDev));
+  L.cs_off = L.ranges_off + align_up((size_t)n_ranges * sizeof(rfx::SegRangeDev));
+  const size_t cand = align_up((size_t)nq * rfx::kSegLists * rfx::seg_k_slot(k) * 4);
+  L.cr_off = L.cs_off + cand;
+  L.total = L.cr_off + cand;
+  return L;
+}
+}  // namespace
+
+extern "C" {
+
+int rfx_search_segmented_workspace_bytes(rfx_index_t h, int64_t nq, int k, int64_t n_ranges, size_t* out_bytes) {
+  auto ix = get(h);
+  if (!ix) return fail(RFX_EINVAL, "unknown index handle");
+  if (!out_bytes) return fail(RFX_EINVAL, "null output");
+  if (k < 1 || k > 64) return fail(RFX_EINVAL, "k=%d out of range [1, 64]", k);
+  if (nq < 0 || nq > rfx::kSegMaxNq) return fail(RFX_EINVAL, "nq=%lld out of [0, %lld]", (long long)nq, (long long)rfx::kSegMaxNq);
+  if (n_ranges < 0 || n_ranges > 0x7fffffffll) return fail(RFX_EINVAL, "n_ranges=%lld out of range", (long long)n_ranges);
+  *out_bytes = seg_layout(nq, k, n_ranges).total;
+  return RFX_OK;
+}
+
+int rfx_segmented_plan(int64_t rows, int dim, int dtype, int64_t nq, int k, int n_groups, const int64_t* group_q_h,
+                       const int64_t* group_r_h, const int64_t* ranges_h, int64_t* items_h, int64_t cap,
+                       int64_t* out_n_items, int* out_lists_per_query) {
+  if (dim <= 0 || dim % 64 != 0 || !valid_dtype(dtype)) return fail(RFX_EINVAL, "bad dim %d / dtype %d", dim, dtype);
+  if (!rfx::seg_supported(dim, dtype)) return fail(RFX_EUNSUPPORTED, "segmented scan: dim %d dtype %d unsupported", dim, dtype);
+  if (cap < 0 || (cap > 0 && !items_h)) return fail(RFX_EINVAL, "bad items buffer");
+  const std::string err = rfx::seg_validate(rows, nq, k, n_groups, group_q_h, group_r_h, ranges_h);
+  if (!err.empty()) return fail(RFX_EINVAL, "segmented search: %s", err.c_str());
+  std::vector<rfx::SegItem> items;
+  const int lists = rfx::seg_plan(nq, n_groups, group_q_h, group_r_h, ranges_h, items);
+  for (int64_t i = 0; i < (int64_t)items.size() && i < cap; ++i) {
+    items_h[4 * i + 0] = items[i].group;
+    items_h[4 * i + 1] = items[i].q0;
+    items_h[4 * i + 2] = items[i].pos0;
+    items_h[4 * i + 3] = items[i].n;
+  }
+  if (out_n_items) *out_n_items = (int64_t)items.size();
+  if (out_lists_per_query) *out_lists_per_query = lists;
+  return RFX_OK;
+}
+
+int rfx_search_segmented(rfx_index_t h, const void* queries_d, int64_t nq, int k, int n_groups,
+                         const int64_t* group_q_h, const int64_t* group_r_h, const int64_t* ranges_h,
+                         float* out_scores_d, int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream) {
+  auto ix = get(h);
+  if (!ix) return fail(RFX_EINVAL, "unknown index handle");
+  RFX_RLOCK(ix);  // the data pointer moves on growth
+  if (!rfx::seg_supported(ix->dim, ix->dtype))
+    return fail(RFX_EUNSUPPORTED, "segmented scan: dim %d dtype %d unsupported", ix->dim, ix->dtype);
+  const std::string err = rfx::seg_validate(ix->rows, nq, k, n_groups, group_q_h, group_r_h, ranges_h);
+  if (!err.empty()) return fail(RFX_EINVAL, "segmented search: %s", err.c_str());
+  if (nq == 0) return RFX_OK;
+  if (!queries_d || !out_scores_d || !out_rows_d) return fail(RFX_EINVAL, "null queries / outputs");
+  const int64_t n_ranges = group_r_h[n_groups];
+  const SegLayout L = seg_layout(nq, k, n_ranges);
+  if (ws_bytes < L.total || !ws_d) return fail(RFX_EINVAL, "workspace too small (%zu < %zu)", ws_bytes, L.total);
+  std::vector<rfx::SegItem> items;
+  const int lists = rfx::seg_plan(nq, n_groups, group_q_h, group_r_h, ranges_h, items);
+  const int64_t n_items = (int64_t)items.size();
+  if (n_items > rfx::seg_max_items(nq)) return fail(RFX_EINVAL, "segmented search: %lld work items", (long long)n_items);
+  RFX_HIP(hipSetDevice(ix->device));
+  hipStream_t st = (hipStream_t)stream;
+  uint8_t* ws = (uint8_t*)ws_d;
+  if (n_items > 0) {
+    // The tables, through the index's pinned staging buffer: the caller's arrays may die on return, and
+    // the copy stays stream-ordered.  One user at a time; the previous copy out of the buffer has finished
+    // (seg_ev) before it is refilled.
+    const size_t items_bytes = (size_t)n_items * sizeof(rfx::SegItemDev);
+    const size_t ranges_bytes = (size_t)n_ranges * sizeof(rfx::SegRangeDev);
+    std::lock_guard<std::mutex> slk(ix->seg_mu);
+    if (!ix->seg_ev) RFX_HIP(hipEventCreateWithFlags(&ix->seg_ev, hipEventDisableTiming));
+    else RFX_HIP(hipEventSynchronize(ix->seg_ev));
+    const size_t need = align_up(items_bytes) + ranges_bytes;
+    if (ix->seg_stage_bytes < need) {
+      if (ix->seg_stage) RFX_HIP(hipHostFree(ix->seg_stage));
+      ix->seg_stage = nullptr;
+      ix->seg_stage_bytes = 0;
+      const size_t want = std::max(need * 2, (size_t)1 << 16);
+      if (hipHostMalloc(&ix->seg_stage, want, hipHostMallocDefault) != hipSuccess)
+        return fail(RFX_ENOMEM, "hipHostMalloc(%zu) failed (segmented search tables)", want);
+      ix->seg_stage_bytes = want;
+    }
+    uint8_t* stage = (uint8_t*)ix->seg_stage;
+    rfx::SegItemDev* it_h = (rfx::SegItemDev*)stage;
+    for (int64_t i = 0; i < n_items; ++i) it_h[i] = rfx::seg_item_dev(items[i]);
+    rfx::seg_ranges_dev(n_groups, group_r_h, ranges_h, (rfx::SegRangeDev*)(stage + align_up(items_bytes)));
+    RFX_HIP(hipMemcpyAsync(ws, stage, items_bytes, hipMemcpyHostToDevice, st));
+    RFX_HIP(hipMemcpyAsync(ws + L.ranges_off, stage + align_up(items_bytes), ranges_bytes, hipMemcpyHostToDevice, st));
+    RFX_HIP(hipEventRecord(ix->seg_ev, st));
+  }
+  float* cs = (float*)(ws + L.cs_off);
+  int* cr = (int*)(ws + L.cr_off);
+  if (rfx::launch_scan_seg(ix->data, (int)ix->rows, ix->dim, ix->dtype, queries_d, nq, k, (const rfx::SegItemDev*)ws,
+                           (int)n_items, (const rfx::SegRangeDev*)(ws + L.ranges_off), cs, cr, lists, st) != 0)
+    return fail(RFX_EUNSUPPORTED, "segmented scan launch rejected");
+  RFX_HIP(hipGetLastError());
+  // the lists are sorted (empty slots last); the final top-k is re-scored by the score rule of every plan
+  const int k_slot = rfx::seg_k_slot(k);
+  const rfx::Rescore rs{ix->data, queries_d, ix->dim, ix->dtype, ix->rows};
+  if (rfx::launch_topk_merge_lists(cs, cr, 0, nq, (int64_t)lists * k_slot, k_slot, k, 0, out_scores_d, out_rows_d,
+                                   nullptr, st, /*sorted=*/true, nullptr, ix->data && ix->rows > 0 ? &rs : nullptr) != 0)
+    return fail(RFX_EUNSUPPORTED, "merge k=%d unsupported", k);
   RFX_HIP(hipGetLastError());
   return RFX_OK;
 }

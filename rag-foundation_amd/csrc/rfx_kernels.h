@@ -5,6 +5,7 @@
 #include <algorithm>
 
 #include "../../include/rfx.h"
+#include "seg_plan.h"
 
 namespace rfx {
 // f64 re-score of a two-pass fallback's final top-k (k_scan_valu.h rescore_final)
@@ -122,6 +123,16 @@ int launch_scan_mfma9(const MfmaPlan& p, const void* X, int nrows, int D, int dt
                       const uint32_t* gate = nullptr, bool tau_zeroed = false);
 void launch_pad_queries(const void* Q, int64_t nq, int64_t nq_pad, int D, int esz, void* out,
                         hipStream_t st);
+
+// ---- segmented scan (k_scan_seg.h): questions under different metadata filters in one launch -----------
+// items / R: the device tables of seg_plan.h (work items, ranges with their positions); cs / cr:
+// [nq][n_lists][seg_k_slot(k)] candidates, filled with empty slots here, then written per item; Q: the
+// queries in the index dtype.  n_items == 0: the fill only.
+int seg_k_slot(int k);
+bool seg_supported(int D, int dtype);
+int launch_scan_seg(const void* X, int nrows, int D, int dtype, const void* Q, int64_t nq, int k,
+                    const SegItemDev* items, int n_items, const SegRangeDev* R, float* cs, int* cr, int n_lists,
+                    hipStream_t st);
 
 // ---- merge -----------------------------------------------------------------------------------
 int launch_topk_merge(const float* cs, const void* cr, int rows_are_i64, int64_t nq, int64_t n_cand,

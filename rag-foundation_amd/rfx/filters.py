@@ -92,6 +92,16 @@ def filter_key(metadata_filter: Optional[Dict[str, Any]]) -> str:
     return json.dumps(metadata_filter, sort_keys=True, separators=(",", ":"))
 
 
+def group_by_filter(metadata_filters) -> list:
+    """Batch items' filters -> [(filter, [item indices])], one entry per distinct filter_key in order of
+    first appearance (equal filters written with another key order share a group), the indices of a
+    group in their batch order: the groups of one segmented search (rfx_search_segmented)."""
+    groups: Dict[str, Tuple[Any, list]] = {}
+    for i, f in enumerate(metadata_filters):
+        groups.setdefault(filter_key(f), (f, []))[1].append(i)
+    return list(groups.values())
+
+
 def row_mask_words(n_rows: int, ranges: Iterable[Tuple[int, int]]) -> np.ndarray:
     """Bitmap of (first, count) row ranges: int32 words, bit (r & 31) of word r >> 5 = row r
     (the layout rfx_search_masked reads), (n_rows + 31) // 32 words (at least one)."""

@@ -194,6 +194,34 @@ class DeviceIndex:
                                             ptr(ws), ws.numel(), stream_ptr(stream)))
         return out_s, out_r
 
+    def search_segmented(self, queries: torch.Tensor, k: int, groups, workspace: torch.Tensor = None, stream=None):
+        """One launch for questions under different metadata filters (rfx_search_segmented): `groups` is a
+        list of (query_indices, [(first, count), ...]); a query is answered over its group's row ranges only
+        (ascending, disjoint, inside the index), and only those rows are read.  Every query belongs to exactly
+        one group.  Returns (scores f32 [nq][k], rows int64 [nq][k]) in the caller's query order; a group
+        without ranges answers padding (-inf, -1)."""
+        q = self._check_queries(queries)
+        nq = q.shape[0]
+        dev = q.device
+        perm, gq, gr, ranges = pack_groups(nq, groups)
+        order = torch.as_tensor(perm, dtype=torch.int64, device=dev)
+        qs = q.index_select(0, order) if nq else q
+        out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        need = ctypes.c_size_t()
+        check(lib.rfx_search_segmented_workspace_bytes(self.handle, nq, int(k), len(ranges) // 2, ctypes.byref(need)))
+        ws = workspace if workspace is not None and workspace.numel() >= need.value else \
+            torch.empty(max(need.value, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.rfx_search_segmented(self.handle, ptr(qs), nq, int(k), len(gq) - 1, gq.ctypes.data,
+                                           gr.ctypes.data, ranges.ctypes.data, ptr(out_s), ptr(out_r), ptr(ws),
+                                           ws.numel(), stream_ptr(stream)))
+        if nq == 0:
+            return out_s, out_r
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(nq, dtype=torch.int64, device=dev)
+        return out_s.index_select(0, inv), out_r.index_select(0, inv)
+
     def search_records(self, queries: torch.Tensor, k: int, row_offset: int = 0, out: torch.Tensor = None,
                        workspace: torch.Tensor = None, stream=None, row_mask: torch.Tensor = None) -> torch.Tensor:
         """The search as [nq][k][2] int64 merge records (score bits, row + row_offset): one shard's
@@ -290,6 +318,50 @@ class DeviceIndex:
                 check(lib.rfx_scan_topk_masked(self.handle, ptr(q), nq, int(k), ptr(m), mw, ptr(cs), ptr(cr),
                                                ptr(ws), ws.numel(), stream_ptr(stream)))
         return cs, cr
+
+
+SEGMENT_LISTS = 64  # L of the segmented search: a group's rows are cut into at most this many chunks
+
+
+def pack_groups(nq: int, groups):
+    """groups [(query_indices, [(first, count), ...])] -> (perm, group_q, group_r, ranges): the arrays of
+    rfx_search_segmented (int64, contiguous); perm[i] = the caller's index of the i-th query in group
+    order.  ValueError unless every query index in [0, nq) appears exactly once."""
+    import numpy as np
+    perm, gq, gr, flat = [], [0], [0], []
+    for qidx, rngs in groups:
+        perm.extend(int(i) for i in qidx)
+        for first, count in rngs:
+            flat.extend((int(first), int(count)))
+        gq.append(len(perm))
+        gr.append(len(flat) // 2)
+    if sorted(perm) != list(range(nq)):
+        raise ValueError(f"groups must hold each of the {nq} query indices exactly once")
+    as64 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.int64))
+    return perm, as64(gq), as64(gr), as64(flat if flat else [0, 0])[:len(flat)]
+
+
+def segmented_plan(rows: int, dim: int, dtype: str, nq: int, k: int, group_q, group_r, ranges):
+    """Host only (rfx_segmented_plan): the work list rfx_search_segmented would run over an index of `rows`
+    rows, as an int64 array [n_items][4] (group, first query, first selected-row position, selected rows),
+    and the candidate lists per query.  ValueError for arguments the search would refuse."""
+    import numpy as np
+    gq = np.ascontiguousarray(np.asarray(group_q, dtype=np.int64))
+    gr = np.ascontiguousarray(np.asarray(group_r, dtype=np.int64))
+    rg = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1))
+    n_groups = len(gq) - 1
+    if n_groups < 0 or len(gr) != len(gq):
+        raise ValueError("group_q / group_r must have n_groups + 1 entries each")
+    if n_groups and (int(gr[-1]) * 2 > rg.size or int(gr.max()) * 2 > rg.size):
+        raise ValueError("group_r points past the ranges")
+    n, lists = ctypes.c_int64(), ctypes.c_int()
+    args = (int(rows), int(dim), _lib.DTYPE_CODES[dtype], int(nq), int(k), n_groups, gq.ctypes.data, gr.ctypes.data,
+            rg.ctypes.data if rg.size else None)
+    check(lib.rfx_segmented_plan(*args, None, 0, ctypes.byref(n), ctypes.byref(lists)))
+    items = np.empty((n.value, 4), dtype=np.int64)
+    check(lib.rfx_segmented_plan(*args, items.ctypes.data if n.value else None, n.value, ctypes.byref(n),
+                                 ctypes.byref(lists)))
+    return items, lists.value
 
 
 def _check_cands(cand_s: torch.Tensor, cand_r: torch.Tensor):

@@ -42,7 +42,8 @@ def _chunking(cfg):
 # (device, dim) and per store — or no two requests would ever share a batch.
 _STATE_LOCK = threading.Lock()
 _EMBEDDERS = {}
-_BATCHERS = {}  # (store name | tuple of names, filter key, registry id) -> GroupBatcher
+_BATCHERS = {}  # (store name | tuple of names, filter key | _FILTERED, registry id) -> GroupBatcher
+_FILTERED = "\x00filtered"  # the one batcher of a store's filtered questions (no filter_key starts with NUL)
 # (tuple of names, registry id) -> UnionView (rfx.union), least recently used first; it follows its
 # members' appends and tombstones in place.  Bounded in device bytes (RFX_UNION_MAX_BYTES, default
 # 32 GiB): the least recently used views are evicted, and a view over its own budget is not built
@@ -53,6 +54,23 @@ _UNION_BYTES = [0]
 
 def union_budget() -> int:
     return int(os.environ.get("RFX_UNION_MAX_BYTES", str(32 << 30)))
+
+
+def segmented_mode() -> str:
+    """RFX_SEGMENTED: "0" = one masked search per distinct filter (a batcher per (store, filter)), "1" = the
+    segmented search for every filtered batch, "auto" (default) = by segmented_max_fraction's rule.  Read at
+    every question: services and tests may change it."""
+    m = os.environ.get("RFX_SEGMENTED", "auto").strip().lower()
+    return m if m in ("0", "1") else "auto"
+
+
+def segmented_max_fraction() -> float:
+    """F of the auto rule (RFX_SEGMENTED_MAX_FRACTION): a filtered batch takes the segmented search when
+    sum over filters of (selected rows x ceil(questions / 8)) <= F x distinct filters x store rows, i.e. when
+    the rows it would read are at most F of what one masked search per filter reads.  Default: the largest
+    swept fraction at which the segmented batch was still the faster one, rounded down to a power of two
+    (tools/bench_filters.py)."""
+    return float(os.environ.get("RFX_SEGMENTED_MAX_FRACTION", "0.5"))
 
 
 def _evict_union(key, closing):
@@ -110,6 +128,7 @@ class GpuRetriever:
         # a question over several stores: one scan of their union (rfx.union; RFX_UNION=0 disables)
         self.union = os.environ.get("RFX_UNION", "1") != "0"
         self.last_path = None  # "union" | "per-store" (tests, diagnostics)
+        self.last_filter_path = None  # "segmented" | "masked": how the last filtered batch was searched
 
     @property
     def registry(self):
@@ -170,27 +189,90 @@ class GpuRetriever:
         mask = st.row_mask(metadata_filter) if metadata_filter is not None else None
         if metadata_filter is not None and mask is None:
             return [None] * len(items)
+        if metadata_filter is not None:
+            self.last_filter_path = "masked"
         return [(st, s, r) for s, r in self._search_store_batch(st, items, mask)]
 
-    def _batcher(self, name, metadata_filter):
-        # one batcher per (store, filter): a launch applies one row mask to all its queries
-        key = (name, filters.filter_key(metadata_filter), id(self.registry))
+    def _run_filtered_batch(self, name, items):
+        """Batch runner of a store's filtered questions, items (question, k, filter): the items are grouped
+        by filter and each group's row ranges resolved (a filter that matches no file answers None); then
+        ONE segmented search reads only the selected rows (DeviceIndex.search_segmented), or, when the
+        filters select too much of the store for that to pay (segmented_max_fraction), one masked search
+        per distinct filter runs as before."""
+        st = self.registry.get(name)
+        out = [None] * len(items)
+        if st is None:
+            return out
+        groups = []  # (filter, item indices, ranges) of the filters that select rows
+        for filt, idxs in filters.group_by_filter([f for _, _, f in items]):
+            ranges = st.segment_ranges(filt)
+            if ranges:
+                groups.append((filt, idxs, ranges))
+        if not groups:
+            return out
+        mode = segmented_mode()
+        if mode == "auto":
+            cost = sum(sum(n for _, n in ranges) * ((len(idxs) + 7) // 8) for _, idxs, ranges in groups)
+            mode = "1" if cost <= segmented_max_fraction() * len(groups) * st.index.rows else "0"
+        if mode == "0":
+            self.last_filter_path = "masked"
+            for filt, idxs, _ in groups:
+                mask = st.row_mask(filt)
+                if mask is None:
+                    continue
+                res = self._search_store_batch(st, [items[i][:2] for i in idxs], mask)
+                for i, (s, r) in zip(idxs, res):
+                    out[i] = (st, s, r)
+            return out
+        self.last_filter_path = "segmented"
+        live = [i for _, idxs, _ in groups for i in idxs]
+        pos = {i: p for p, i in enumerate(live)}
+        kmax = max(items[i][1] for i in live)
+        with torch.cuda.device(st.device):
+            q = self.embedder(st.dim).embed_texts([items[i][0] for i in live], st.dtype)
+            s, r = st.index.search_segmented(q, kmax, [([pos[i] for i in idxs], ranges) for _, idxs, ranges in groups])
+            s, r = s.cpu().tolist(), r.cpu().tolist()
+        for i in live:
+            k = items[i][1]
+            out[i] = (st, s[pos[i]][:k], r[pos[i]][:k])
+        return out
+
+    def _batcher(self, name, metadata_filter, shared=False):
+        # masked searches: one batcher per (store, filter), a launch applies one row mask to all its queries;
+        # shared: the store's ONE batcher of filtered questions (items carry their filter: _run_filtered_batch)
+        key = (name, _FILTERED if shared else filters.filter_key(metadata_filter), id(self.registry))
         with _STATE_LOCK:
             b = _BATCHERS.get(key)
             if b is None:
                 if self.registry.on_evict.count(_purge_batchers) == 0:
                     self.registry.on_evict.append(_purge_batchers)
-                b = GroupBatcher(lambda items, n=name, f=metadata_filter: self._run_batch(n, f, items),
-                                 max_batch=256)
+                if shared:
+                    b = GroupBatcher(lambda items, n=name: self._run_filtered_batch(n, items), max_batch=256)
+                else:
+                    b = GroupBatcher(lambda items, n=name, f=metadata_filter: self._run_batch(n, f, items),
+                                     max_batch=256)
                 if len(_BATCHERS) >= 4096:
                     _BATCHERS.clear()
                 _BATCHERS[key] = b
             return b
 
+    def _segmentable(self, name):
+        """Filtered questions of this store go through the shared batcher: a single-device flat index
+        (sharded stores keep one masked search per filter), unless RFX_SEGMENTED=0."""
+        if segmented_mode() == "0":
+            return False
+        st = self.registry.get(name)
+        return st is not None and hasattr(st.index, "search_segmented") and hasattr(st, "segment_ranges")
+
     def search_store(self, name, question, k, metadata_filter=None):
         """(store, scores, rows) of one question against one store, or None when the store is
         gone or the filter selects no row of it; batched with concurrent callers of the same
-        store and filter."""
+        store (filtered questions of a store share one batch, whatever their filters)."""
+        if metadata_filter is not None and self._segmentable(name):
+            item = (question, int(k), metadata_filter)
+            if self.batching:
+                return self._batcher(name, None, shared=True).submit(item)
+            return self._run_filtered_batch(name, [item])[0]
         if self.batching:
             return self._batcher(name, metadata_filter).submit((question, int(k)))
         return self._run_batch(name, metadata_filter, [(question, int(k))])[0]

@@ -137,6 +137,7 @@ class LocalStore:
         self.lock = threading.RLock()
         self._stat = None
         self._masks = {}    # (version, filter key) -> device row mask
+        self._ranges = {}   # (version, filter key, form) -> (first, count) row ranges
         self._screen_on = False  # the index holds the two-pass scan's int8 copy (_maybe_screen)
         self.spec = {"kind": "flat"}
         self.ivf_meta = None  # committed {"id", "rows"} of the current centroids
@@ -238,6 +239,7 @@ class LocalStore:
         self.meta_bytes = self.files_bytes = self.tombs = 0
         self.version = -1
         self._masks = {}
+        self._ranges = {}
         self._screen_on = False
 
     def _sync(self, man=None, stat=None):
@@ -515,11 +517,34 @@ class LocalStore:
             return mask
 
     def mask_ranges(self, metadata_filter):
-        """(first, count) row ranges of the live files whose upload metadata matches the filter."""
+        """(first, count) row ranges of the live files whose upload metadata matches the filter, in file
+        order.  Cached per (store version, filter), as row_mask; callers do not change the list."""
         with self.lock:
-            return [(f["first"], f["n"]) for f in self.files.values()
-                    if not f["deleted"] and f["n"] and
-                    filters.file_matches(filters.normalize_metadata(f.get("metadata")), metadata_filter)]
+            key = (self.version, filters.filter_key(metadata_filter), "files")
+            if key not in self._ranges:
+                if len(self._ranges) >= 256:
+                    self._ranges.clear()
+                self._ranges[key] = [(f["first"], f["n"]) for f in self.files.values()
+                                     if not f["deleted"] and f["n"] and
+                                     filters.file_matches(filters.normalize_metadata(f.get("metadata")), metadata_filter)]
+            return self._ranges[key]
+
+    def segment_ranges(self, metadata_filter):
+        """mask_ranges in ascending row order with touching ranges joined (files own disjoint row ranges):
+        the form the segmented search takes (DeviceIndex.search_segmented).  Cached the same way."""
+        with self.lock:
+            key = (self.version, filters.filter_key(metadata_filter), "sorted")
+            if key not in self._ranges:
+                out = []
+                for first, n in sorted(self.mask_ranges(metadata_filter)):
+                    if out and out[-1][0] + out[-1][1] == first:
+                        out[-1] = (out[-1][0], out[-1][1] + n)
+                    else:
+                        out.append((first, n))
+                if len(self._ranges) >= 256:
+                    self._ranges.clear()
+                self._ranges[key] = out
+            return self._ranges[key]
 
     def row_info(self, row):
         """(file_id, chunk text, title, uri) of a row, or None for a row this process has no
