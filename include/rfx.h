@@ -104,6 +104,31 @@ int rfx_index_add_synthetic(rfx_index_t h, uint64_t seed, int64_t gen_row0, int6
 /* Tombstone rows (delete_document_from_store gemini_rag.py:392-424): the rows' vectors are
  * overwritten with NaN on the device so no scan can ever rank them. */
 int rfx_index_tombstone(rfx_index_t h, const int64_t* rows_h, int64_t n, void* stream);
+/* Compaction: give back the rows of deleted documents (delete_document_from_store, gemini_rag.py:392-424,
+ * only tombstones them: they stay in device memory and every scan streams them).  ranges_h holds n_ranges
+ * KEEP ranges {first, count}: ascending, disjoint, count > 0, inside [0, rows); anything else is RFX_EINVAL
+ * before the index is touched, as is a union view.  The kept rows are gathered, in order, into a FRESH
+ * allocation sized as growth would size it for their number (one kernel launch however many ranges there
+ * are; out of place: the old allocation is released after a device synchronisation, so the memory returns).
+ * Kept row p of the result is the old row first_i + (p - kept rows before range i); a kept row that was
+ * tombstoned stays NaN and tombstoned.  The int8 copy of the two-pass scan, when on, is freed and rebuilt
+ * over the kept rows, so its store-wide maxima are theirs (RFX_ECAPACITY at the rebuild: the copy is
+ * dropped as after an append that outgrows it, and the call succeeds).  Ranges that keep every row return
+ * RFX_OK with nothing moved; keeping no row leaves an empty index.  RFX_ENOMEM for the new rows leaves the
+ * index as it was.  Row ids change: union views over the index become stale (rfx_union_refresh).
+ * *out_rows (may be NULL) = the rows kept. */
+int rfx_index_compact(rfx_index_t h, const int64_t* ranges_h, int64_t n_ranges, int64_t* out_rows, void* stream);
+/* What the phases of the index's last compaction took, in ms: out_ms[5] = the gather kernel (HIP events around
+ * the launch), the new allocation + table upload + NaN tail, the release of the old rows (device
+ * synchronise, unmap), the host bitmap, the int8 copy's rebuild (host clock).  Zeros before the first one. */
+int rfx_index_compact_times(rfx_index_t h, double* out_ms);
+/* Host only (no device call): what rfx_index_compact would do with the ranges over an index of `rows` rows.
+ * table_h (may be NULL) receives per range {source first row, destination first row} (the prefix sum of the
+ * counts); chunks_h (may be NULL with cap 0: count only) the first cap work chunks {first kept position,
+ * positions}: they tile [0, kept) exactly once, a chunk may span several ranges, and there are at most 4,096
+ * of max(32, ceil(kept / 4096)) positions rounded up to 32.  RFX_EINVAL for ranges the compaction refuses. */
+int rfx_compact_plan(int64_t rows, const int64_t* ranges_h, int64_t n_ranges, int64_t* table_h /* [n_ranges][2] */,
+                     int64_t* chunks_h /* [cap][2] */, int64_t cap, int64_t* out_kept, int64_t* out_n_chunks);
 /* Copy rows [row0, row0+n) to dst (device or host). */
 int rfx_index_read(rfx_index_t h, int64_t row0, int64_t n, void* dst, int dst_is_device, void* stream);
 /* Device pointer to row 0 (row-major [capacity][dim] of dtype).  Valid until next add. */

@@ -33,6 +33,7 @@
 #include <string>
 #include <vector>
 
+#include "k_compact.h"
 #include "rfx_kernels.h"
 
 namespace {
@@ -194,6 +195,9 @@ struct Index {
   // exact fallback (tests of the fallback path).
   int screen = 0;
   int screen_dropped = 0;  // an append outgrew what the copy could follow: dropped, the index is exact
+  // the last compaction's phases in ms (rfx_index_compact_times): gather kernel (events), new allocation +
+  // table upload + NaN tail, release of the old rows, host bitmap, int8 copy rebuild
+  double compact_ms[5] = {0, 0, 0, 0, 0};
   int64_t scap = 0;
   int8_t* scodes = nullptr;
   void* smeta = nullptr;  // per tile {f32 scale, u32 live word, 0, 0}
@@ -364,15 +368,17 @@ std::shared_ptr<Index> get(rfx_index_t h) {
 
 // Invariant: rows [rows, capacity) of the device buffer hold NaN, so a scan tile that runs past
 // the last row (capacity is a multiple of 128 rows) reads rows that can never be ranked.
-int fill_tail_nan(Index& ix, hipStream_t st) {
-  const int64_t n = ix.capacity - ix.rows;
+// rows [row0, cap) of a row buffer `data` of the index's geometry
+int fill_nan_rows(const Index& ix, void* data, int64_t row0, int64_t cap, hipStream_t st) {
+  const int64_t n = cap - row0;
   if (n <= 0) return RFX_OK;
   const uint32_t pattern = ix.dtype == RFX_F32 ? 0x7fc00000u : (ix.dtype == RFX_BF16 ? 0x7fc07fc0u : 0x7e007e00u);
-  RFX_HIP(hipMemsetD32Async((hipDeviceptr_t)((uint8_t*)ix.data + ix.rows * ix.row_bytes()), (int)pattern,
+  RFX_HIP(hipMemsetD32Async((hipDeviceptr_t)((uint8_t*)data + row0 * ix.row_bytes()), (int)pattern,
                             (size_t)(n * ix.row_bytes() / 4), st));
   RFX_HIP(hipStreamSynchronize(st));
   return RFX_OK;
 }
+int fill_tail_nan(Index& ix, hipStream_t st) { return fill_nan_rows(ix, ix.data, ix.rows, ix.capacity, st); }
 
 // Capacity granule (rows): whole 128-row scan tiles; with virtual memory also a whole number of granules of
 // the rows' bytes AND of the int8 copy's (d bytes per row), so members of a union view map back to back at
@@ -383,32 +389,52 @@ int64_t capacity_align(const Index& ix) {
   return lcm64(lcm64(128, g / gcd64(g, ix.row_bytes())), g / gcd64(g, (int64_t)ix.dim));
 }
 
-int grow(Index& ix, int64_t need, hipStream_t st) {
-  if (need <= ix.capacity) return RFX_OK;
-  int64_t cap = ix.capacity > 0 ? ix.capacity : 1024;
+// The capacity a buffer of `from` rows grows to so that it holds `need` (> from): geometric, whole granules.
+int64_t grown_capacity(const Index& ix, int64_t from, int64_t need) {
+  int64_t cap = from > 0 ? from : 1024;
   while (cap < need) cap = cap + cap / 2 + 1024;
   const int64_t al = capacity_align(ix);
-  cap = (cap + al - 1) / al * al;
-  void* p = nullptr;
-  std::shared_ptr<Mapping> m;
+  return (cap + al - 1) / al * al;
+}
+
+// a fresh row buffer of `cap` rows: virtual memory where the device has it, else hipMalloc
+int alloc_rows(const Index& ix, int64_t cap, void** p, std::shared_ptr<Mapping>& m) {
   const size_t bytes = (size_t)cap * ix.row_bytes();
   if (vmm_granularity(ix.device)) {
     const int rc = vmm_alloc(ix.device, bytes, m);
     if (rc) return fail(RFX_ENOMEM, "device memory for %lld rows: %s", (long long)cap, g_err.c_str());
-    p = m->va;
-  } else if (hipMalloc(&p, bytes) != hipSuccess) {
+    *p = m->va;
+  } else if (hipMalloc(p, bytes) != hipSuccess) {
     return fail(RFX_ENOMEM, "hipMalloc(%zu) failed for index", bytes);
   }
-  if (ix.rows > 0) {
-    RFX_HIP(hipMemcpyAsync(p, ix.data, (size_t)ix.rows * ix.row_bytes(), hipMemcpyDeviceToDevice, st));
-    RFX_HIP(hipStreamSynchronize(st));
-  }
+  return RFX_OK;
+}
+
+// give the index's row buffer back (the caller installs another, or none)
+int release_rows(Index& ix) {
   if (ix.rows_map) {
     RFX_HIP(hipDeviceSynchronize());  // no search still reads the old rows: then unmap
     ix.rows_map.reset();
   } else if (ix.data) {
     RFX_HIP(hipFree(ix.data));  // hipFree waits for in-flight work on the old buffer
   }
+  ix.data = nullptr;
+  return RFX_OK;
+}
+
+int grow(Index& ix, int64_t need, hipStream_t st) {
+  if (need <= ix.capacity) return RFX_OK;
+  const int64_t cap = grown_capacity(ix, ix.capacity, need);
+  void* p = nullptr;
+  std::shared_ptr<Mapping> m;
+  const int rc = alloc_rows(ix, cap, &p, m);
+  if (rc) return rc;
+  if (ix.rows > 0) {
+    RFX_HIP(hipMemcpyAsync(p, ix.data, (size_t)ix.rows * ix.row_bytes(), hipMemcpyDeviceToDevice, st));
+    RFX_HIP(hipStreamSynchronize(st));
+  }
+  const int rr = release_rows(ix);
+  if (rr) return rr;
   ix.rows_map = m;
   ix.data = p;
   ix.capacity = cap;
@@ -2277,6 +2303,205 @@ int rfx_search_segmented(rfx_index_t h, const void* queries_d, int64_t nq, int k
                                    nullptr, st, /*sorted=*/true, nullptr, ix->data && ix->rows > 0 ? &rs : nullptr) != 0)
     return fail(RFX_EUNSUPPORTED, "merge k=%d unsupported", k);
   RFX_HIP(hipGetLastError());
+  return RFX_OK;
+}
+
+// ---- store compaction: reclaim the rows of deleted documents ------------------------------------------------
+// (delete_document_from_store, gemini_rag.py:392-424, only tombstones; kernel: k_compact.h, plan: compact_plan.h)
+}  // extern "C"
+namespace {
+double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+// set bits of the bitmap among rows [r0, r0 + n)
+int64_t tomb_count(const std::vector<uint8_t>& tomb, int64_t r0, int64_t n) {
+  int64_t c = 0, r = r0;
+  const int64_t e = r0 + n;
+  for (; r < e && (r & 7); ++r) c += (tomb[(size_t)r >> 3] >> (r & 7)) & 1;
+  for (; r + 64 <= e; r += 64) {
+    uint64_t w;
+    memcpy(&w, &tomb[(size_t)r >> 3], 8);
+    c += __builtin_popcountll(w);
+  }
+  for (; r + 8 <= e; r += 8) c += __builtin_popcount(tomb[(size_t)r >> 3]);
+  for (; r < e; ++r) c += (tomb[(size_t)r >> 3] >> (r & 7)) & 1;
+  return c;
+}
+}  // namespace
+extern "C" {
+
+int rfx_compact_plan(int64_t rows, const int64_t* ranges_h, int64_t n_ranges, int64_t* table_h, int64_t* chunks_h,
+                     int64_t cap, int64_t* out_kept, int64_t* out_n_chunks) {
+  if (cap < 0 || (cap > 0 && !chunks_h)) return fail(RFX_EINVAL, "bad chunks buffer");
+  const std::string err = rfx::compact_validate(rows, ranges_h, n_ranges);
+  if (!err.empty()) return fail(RFX_EINVAL, "compaction: %s", err.c_str());
+  std::vector<rfx::CompactRangeDev> table;
+  std::vector<rfx::CompactChunkDev> chunks;
+  const int64_t kept = rfx::compact_plan(ranges_h, n_ranges, table, chunks);
+  if (table_h)
+    for (size_t i = 0; i < table.size(); ++i) {
+      table_h[2 * i + 0] = table[i].row0;
+      table_h[2 * i + 1] = table[i].pos0;
+    }
+  for (int64_t i = 0; i < (int64_t)chunks.size() && i < cap; ++i) {
+    chunks_h[2 * i + 0] = chunks[(size_t)i].pos0;
+    chunks_h[2 * i + 1] = chunks[(size_t)i].n;
+  }
+  if (out_kept) *out_kept = kept;
+  if (out_n_chunks) *out_n_chunks = (int64_t)chunks.size();
+  return RFX_OK;
+}
+
+int rfx_index_compact(rfx_index_t h, const int64_t* ranges_h, int64_t n_ranges, int64_t* out_rows, void* stream) {
+  auto ix = get(h);
+  if (!ix) return fail(RFX_EINVAL, "unknown index handle");
+  hipStream_t st = (hipStream_t)stream;
+  RFX_WLOCK(ix);  // (a union view: RFX_EINVAL)
+  const std::string err = rfx::compact_validate(ix->rows, ranges_h, n_ranges);
+  if (!err.empty()) return fail(RFX_EINVAL, "compaction: %s", err.c_str());
+  std::vector<rfx::CompactRangeDev> table;
+  std::vector<rfx::CompactChunkDev> chunks;
+  const int64_t kept = rfx::compact_plan(ranges_h, n_ranges, table, chunks);
+  if (out_rows) *out_rows = kept;
+  if (kept == ix->rows) return RFX_OK;  // every row kept: nothing moves
+  RFX_HIP(hipSetDevice(ix->device));
+  // what the phases of this call took (rfx_index_compact_times): the gather by events, the rest by the host clock
+  double times[5] = {0, 0, 0, 0, 0};
+  const auto t_start = std::chrono::steady_clock::now();
+
+  // The new rows first: a failure here leaves the index exactly as it was.  When memory is short, the int8
+  // copy (rebuilt below anyway) makes room for a second attempt.
+  const int64_t cap = kept > 0 ? grown_capacity(*ix, 0, kept) : 0;
+  const int screen_mode = ix->screen;
+  void* p = nullptr;
+  std::shared_ptr<Mapping> m;
+  if (kept > 0) {
+    const size_t tab_bytes = table.size() * sizeof(rfx::CompactRangeDev);
+    const size_t tables = tab_bytes + chunks.size() * sizeof(rfx::CompactChunkDev);
+    uint8_t* tab_d = nullptr;
+    bool copy_freed = false;
+    int rc = alloc_rows(*ix, cap, &p, m);
+    if (rc == RFX_ENOMEM && ix->scodes) {
+      m.reset();
+      RFX_HIP(hipDeviceSynchronize());  // no search still reads the copy
+      screen_free(*ix);
+      copy_freed = true;
+      rc = alloc_rows(*ix, cap, &p, m);
+    }
+    auto drop_new = [&] {
+      if (!m && p) (void)hipFree(p);
+      m.reset();
+      p = nullptr;
+    };
+    if (rc == RFX_OK && hipMalloc(&tab_d, tables) != hipSuccess) {
+      drop_new();
+      rc = fail(RFX_ENOMEM, "hipMalloc(%zu) failed (compaction tables)", tables);
+    }
+    // a failure from here on leaves the rows as they were; an int8 copy that was freed to make room is
+    // built again over them, or marked dropped when it cannot return (the caller's error message is kept)
+    auto restore_copy = [&](int code) {
+      if (!copy_freed) return code;
+      const std::string why = g_err;
+      if (screen_build(*ix, st) != RFX_OK) {
+        screen_free(*ix);
+        ix->screen = 0;
+        ix->screen_dropped = 1;
+      }
+      return fail(code, "%s", why.c_str());
+    };
+    if (rc) return restore_copy(rc);
+    const rfx::CompactRangeDev* ranges_d = (const rfx::CompactRangeDev*)tab_d;
+    const rfx::CompactChunkDev* chunks_d = (const rfx::CompactChunkDev*)(tab_d + tab_bytes);
+    // from here on a failure gives the new rows, the tables and the events back: the index is as it was
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    auto give_up = [&](int code) {
+      (void)hipFree(tab_d);
+      if (ev0) (void)hipEventDestroy(ev0);
+      if (ev1) (void)hipEventDestroy(ev1);
+      drop_new();
+      return restore_copy(code);
+    };
+#define RFX_HIP_NEW(call)                                                                               \
+  do {                                                                                                  \
+    hipError_t e_ = (call);                                                                             \
+    if (e_ != hipSuccess) return give_up(fail(RFX_EDEVICE, "%s: %s", #call, hipGetErrorString(e_)));    \
+  } while (0)
+    RFX_HIP_NEW(hipEventCreate(&ev0));
+    RFX_HIP_NEW(hipEventCreate(&ev1));
+    RFX_HIP_NEW(hipMemcpyAsync(tab_d, table.data(), tab_bytes, hipMemcpyHostToDevice, st));
+    RFX_HIP_NEW(hipMemcpyAsync(tab_d + tab_bytes, chunks.data(), tables - tab_bytes, hipMemcpyHostToDevice, st));
+    RFX_HIP_NEW(hipEventRecord(ev0, st));
+    if (rfx::launch_compact_rows(ix->data, ix->rows, p, kept, ix->row_bytes(), chunks_d, (int)chunks.size(), ranges_d,
+                                 (int)table.size(), st) != 0)
+      return give_up(fail(RFX_EINVAL, "compaction launch rejected"));
+    RFX_HIP_NEW(hipGetLastError());
+    RFX_HIP_NEW(hipEventRecord(ev1, st));
+    rc = fill_nan_rows(*ix, p, kept, cap, st);  // (synchronises the stream: the gather has finished)
+    if (rc) return give_up(rc);
+    float gather_ms = 0.f;
+    RFX_HIP_NEW(hipEventElapsedTime(&gather_ms, ev0, ev1));
+#undef RFX_HIP_NEW
+    times[0] = gather_ms;
+    (void)hipEventDestroy(ev0);
+    (void)hipEventDestroy(ev1);
+    RFX_HIP(hipFree(tab_d));
+  }
+  times[1] = ms_since(t_start) - times[0];  // allocation, mapping, table upload, NaN tail
+  auto t_phase = std::chrono::steady_clock::now();
+  // the int8 copy of the old rows goes with them; it is rebuilt over the kept rows below
+  if (ix->scodes) {
+    RFX_HIP(hipDeviceSynchronize());
+    screen_free(*ix);
+  }
+  int rc = release_rows(*ix);
+  if (rc) return rc;
+  ix->rows_map = m;
+  ix->data = p;
+  ix->capacity = cap;
+  ++ix->layout_gen;
+  times[2] = ms_since(t_phase);
+  t_phase = std::chrono::steady_clock::now();
+
+  // The host bitmap follows the rows.  A range without a tombstone (every range of a store's compaction:
+  // it keeps live files only) costs a popcount over its bytes, not a walk over its rows.
+  std::vector<uint8_t> tomb((size_t)(kept + 7) / 8, 0);
+  int64_t live = kept, pos = 0;
+  for (int64_t i = 0; i < n_ranges; ++i) {
+    const int64_t r0 = ranges_h[2 * i], n = ranges_h[2 * i + 1];
+    if (tomb_count(ix->tomb, r0, n) > 0)
+      for (int64_t j = 0; j < n; ++j)
+        if (ix->tomb[(size_t)(r0 + j) >> 3] & (1u << ((r0 + j) & 7))) {
+          tomb[(size_t)(pos + j) >> 3] |= (uint8_t)(1u << ((pos + j) & 7));
+          --live;
+        }
+    pos += n;
+  }
+  ix->tomb.swap(tomb);
+  ix->rows = kept;
+  ix->live = live;
+  times[3] = ms_since(t_phase);
+  t_phase = std::chrono::steady_clock::now();
+
+  if (screen_mode) {  // the copy over the kept rows: its maxima are theirs
+    rc = screen_build(*ix, st);
+    if (rc == RFX_ECAPACITY) {  // as an append that outgrows the copy: dropped, the index answers exactly
+      screen_free(*ix);
+      ix->screen = 0;
+      ix->screen_dropped = 1;
+      rc = RFX_OK;
+    }
+    if (rc) return rc;
+  }
+  times[4] = ms_since(t_phase);
+  std::copy(times, times + 5, ix->compact_ms);
+  return RFX_OK;
+}
+
+int rfx_index_compact_times(rfx_index_t h, double* out_ms) {
+  auto ix = get(h);
+  if (!ix || !out_ms) return fail(RFX_EINVAL, "unknown index handle / null out");
+  RFX_RLOCK(ix);
+  std::copy(ix->compact_ms, ix->compact_ms + 5, out_ms);
   return RFX_OK;
 }
 

@@ -108,6 +108,9 @@ SIGNATURES = {
     "rfx_index_add_synthetic": ([_u64, _u64, _i64, _i64, _pi64, _p], _i),
     "rfx_index_write": ([_u64, _i64, _p, _i64, _i, _p], _i),
     "rfx_index_tombstone": ([_u64, _pi64, _i64, _p], _i),
+    "rfx_index_compact": ([_u64, _p, _i64, _pi64, _p], _i),
+    "rfx_index_compact_times": ([_u64, _p], _i),
+    "rfx_compact_plan": ([_i64, _p, _i64, _p, _p, _i64, _pi64, _pi64], _i),
     "rfx_index_read": ([_u64, _i64, _i64, _p, _i, _p], _i),
     "rfx_index_data": ([_u64, _pp], _i),
     "rfx_index_save": ([_u64, _cs], _i),

@@ -137,6 +137,13 @@ class LocalGpuRag:
             return
         self.retriever.delete_file(store_name, file_id)
 
+    def compact_store(self, store_name: str) -> dict:
+        """Reclaim the rows of deleted documents: {"rows_before", "rows", "seconds"}.  The reference has no
+        counterpart (the hosted store does this out of sight); the app calls it after
+        delete_document_from_store or from its periodic cleanup.  RFX_COMPACT=auto lets
+        deletes do it on their own (rfx.store.compact_policy)."""
+        return self.retriever.compact_store(store_name)
+
     # -------- Query (sync & stream) --------
     def retrieve(self, question: str, store_names: Sequence[str], k: Optional[int] = None,
                  metadata_filter: Optional[Any] = None):

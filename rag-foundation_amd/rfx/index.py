@@ -142,6 +142,25 @@ class DeviceIndex:
             check(lib.rfx_index_tombstone(self.handle, arr.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), arr.size,
                                           stream_ptr()))
 
+    def compact(self, ranges) -> int:
+        """Keep only the rows of `ranges` [(first, count), ...] (ascending, disjoint), gathered in order into
+        a fresh, smaller allocation (rfx_index_compact); the int8 copy is rebuilt over them.  Row ids change:
+        kept row p is the p-th row of the ranges.  Returns the rows kept.  ValueError for ranges the library
+        refuses, before anything moved."""
+        arr = _ranges_array(ranges)
+        kept = ctypes.c_int64()
+        with torch.cuda.device(self.device):
+            check(lib.rfx_index_compact(self.handle, arr.ctypes.data if arr.size else None, arr.shape[0],
+                                        ctypes.byref(kept), stream_ptr()))
+        return kept.value
+
+    def compact_times(self) -> dict:
+        """The last compact()'s phases in ms (rfx_index_compact_times): gather = the kernel by HIP events;
+        alloc, release, bitmap, screen by the host clock."""
+        ms = (ctypes.c_double * 5)()
+        check(lib.rfx_index_compact_times(self.handle, ctypes.cast(ms, ctypes.c_void_p)))
+        return dict(zip(("gather", "alloc", "release", "bitmap", "screen"), (float(v) for v in ms)))
+
     def read(self, row0: int, n: int) -> torch.Tensor:
         out = torch.empty((n, self.dim), dtype=self.torch_dtype, device=self._dev())
         with torch.cuda.device(self.device):
@@ -362,6 +381,30 @@ def segmented_plan(rows: int, dim: int, dtype: str, nq: int, k: int, group_q, gr
     check(lib.rfx_segmented_plan(*args, items.ctypes.data if n.value else None, n.value, ctypes.byref(n),
                                  ctypes.byref(lists)))
     return items, lists.value
+
+
+def _ranges_array(ranges):
+    import numpy as np
+    arr = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1, 2))
+    return arr
+
+
+def compact_plan(rows: int, ranges):
+    """Host only (rfx_compact_plan): what DeviceIndex.compact would do with keep ranges [(first, count), ...]
+    over an index of `rows` rows: (kept rows, table int64 [n_ranges][2] = source first row, destination first
+    row; chunks int64 [n_chunks][2] = first kept position, positions).  ValueError for ranges the compaction
+    refuses."""
+    import numpy as np
+    arr = _ranges_array(ranges)
+    kept, n = ctypes.c_int64(), ctypes.c_int64()
+    rp = arr.ctypes.data if arr.size else None
+    check(lib.rfx_compact_plan(int(rows), rp, arr.shape[0], None, None, 0, ctypes.byref(kept), ctypes.byref(n)))
+    table = np.empty((arr.shape[0], 2), dtype=np.int64)
+    chunks = np.empty((n.value, 2), dtype=np.int64)
+    check(lib.rfx_compact_plan(int(rows), rp, arr.shape[0], table.ctypes.data if table.size else None,
+                               chunks.ctypes.data if chunks.size else None, n.value, ctypes.byref(kept),
+                               ctypes.byref(n)))
+    return kept.value, table, chunks
 
 
 def _check_cands(cand_s: torch.Tensor, cand_r: torch.Tensor):

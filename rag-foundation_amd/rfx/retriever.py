@@ -73,6 +73,30 @@ def segmented_max_fraction() -> float:
     return float(os.environ.get("RFX_SEGMENTED_MAX_FRACTION", "0.5"))
 
 
+class _StoreAnswer(tuple):
+    """(store, scores, rows) of one question, plus .generation: the store generation whose row numbering
+    `rows` uses (LocalStore.row_info translates or refuses rows of an earlier one after a compaction)."""
+    generation = None
+
+
+def _answer(st, s, r, generation):
+    a = _StoreAnswer((st, s, r))
+    a.generation = generation
+    return a
+
+
+def _numbered(st, fn):
+    """fn() -> result, run under one row numbering of `st`: (result, generation).  A compaction that
+    renumbers the store's rows while fn resolves masks or ranges and searches makes it run again."""
+    if not hasattr(st, "numbering"):
+        return fn(), None
+    while True:
+        token, generation = st.numbering()
+        out = fn()
+        if not st.numbering_changed(token):
+            return out, generation
+
+
 def _evict_union(key, closing):
     """(caller holds _STATE_LOCK) Drop the view from the cache; an unpinned view goes to `closing`, which the
     caller closes after releasing the lock.  Its bytes stay counted until it is closed (a pinned view's
@@ -169,6 +193,15 @@ class GpuRetriever:
         st = self.registry.get(store_name)
         return bool(st and st.delete_file(file_id))
 
+    def compact_store(self, name):
+        """Rewrite the store without the rows of its deleted documents (LocalStore.compact):
+        {"rows_before", "rows", "seconds"}.  ValueError for an unknown store."""
+        st = self.registry.get(name)
+        if st is None:
+            raise ValueError(f"unknown store {name!r}")
+        with torch.cuda.device(st.device):
+            return st.compact()
+
     # ---- retrieval ----------------------------------------------------------------------------
     def _search_store_batch(self, st, items, row_mask=None):
         """One GPU search for a batch of (question, k) against one store: one embedding GEMM,
@@ -186,12 +219,18 @@ class GpuRetriever:
         st = self.registry.get(name)
         if st is None:
             return [None] * len(items)
-        mask = st.row_mask(metadata_filter) if metadata_filter is not None else None
-        if metadata_filter is not None and mask is None:
+        def run():
+            mask = st.row_mask(metadata_filter) if metadata_filter is not None else None
+            if metadata_filter is not None and mask is None:
+                return None
+            return self._search_store_batch(st, items, mask)
+
+        res, gen = _numbered(st, run)
+        if res is None:
             return [None] * len(items)
         if metadata_filter is not None:
             self.last_filter_path = "masked"
-        return [(st, s, r) for s, r in self._search_store_batch(st, items, mask)]
+        return [_answer(st, s, r, gen) for s, r in res]
 
     def _run_filtered_batch(self, name, items):
         """Batch runner of a store's filtered questions, items (question, k, filter): the items are grouped
@@ -200,9 +239,13 @@ class GpuRetriever:
         filters select too much of the store for that to pay (segmented_max_fraction), one masked search
         per distinct filter runs as before."""
         st = self.registry.get(name)
-        out = [None] * len(items)
         if st is None:
-            return out
+            return [None] * len(items)
+        out, gen = _numbered(st, lambda: self._filtered_batch(st, items))
+        return [None if o is None else _answer(*o, gen) for o in out]
+
+    def _filtered_batch(self, st, items):
+        out = [None] * len(items)
         groups = []  # (filter, item indices, ranges) of the filters that select rows
         for filt, idxs in filters.group_by_filter([f for _, _, f in items]):
             ranges = st.segment_ranges(filt)
@@ -368,9 +411,11 @@ class GpuRetriever:
                 s, r = view.index.search(q, kmax, row_mask=mask)
                 s, r = s.cpu().numpy(), r.cpu().numpy()
             si, lr = view.locate(r)
+            # (the members' locks are held: no compaction renumbers them between the search and here)
+            gens = [getattr(st, "generation", None) for st in stores]
             out = []
             for i, (_, k) in enumerate(items):
-                out.append([(float(s[i, j]), int(si[i, j]), int(lr[i, j]), stores[si[i, j]])
+                out.append([(float(s[i, j]), int(si[i, j]), int(lr[i, j]), stores[si[i, j]], gens[si[i, j]])
                             for j in range(k) if r[i, j] >= 0])
             return out
         finally:
@@ -407,8 +452,8 @@ class GpuRetriever:
             if res is not None:
                 self.last_path = "union"
                 hits = []
-                for sc, si, row, st in res:
-                    info = st.row_info(row)
+                for sc, si, row, st, gen in res:
+                    info = st.row_info(row, gen)
                     if info is None:
                         continue
                     fid, text, title, uri = info
@@ -424,8 +469,9 @@ class GpuRetriever:
             if res is None:
                 continue
             st, s, r = res
+            gen = getattr(res, "generation", None)
             for sc, row in zip(s, r):
-                info = st.row_info(row) if row >= 0 else None
+                info = st.row_info(row, gen) if row >= 0 else None
                 if info is None:
                     continue
                 fid, text, title, uri = info

@@ -20,6 +20,13 @@ On-disk layout of a store (directory <root>/<store id>/), every data file APPEND
   .lock         fcntl writer lock: appends from several processes (ARQ worker max_jobs=10,
                 worker.py:125; several workers) serialise on it, each first catching up with
                 what the others committed.
+  g-<generation>/  after a compaction (compact()): the directory of the four data files
+                above, named by the manifest's "data_dir" (absent: the store directory itself).  A
+                compaction writes a whole new generation there (the kept byte ranges of rows.rfx, the
+                live rows' metadata, one add record per live file, an empty tombs.bin), commits it
+                with one manifest ("compacted": {"from_generation", "from_version", "rows_before",
+                "rows", "meta_bytes", "files_bytes"}) and removes the old data files; a g-* directory
+                no manifest names is removed by the next writer.
 An upload costs O(its own rows) of disk and device work; a reader (API process) that sees a
 newer manifest loads only what was appended since its last look (rows, metadata, tombstones).
 
@@ -33,8 +40,10 @@ tombstones, NaN there, never return); filtered searches and untrained stores use
 GPU state is a process-level singleton (StoreRegistry), because get_rag_client() builds a new
 adapter per request (chat.py:937, ingestion.py:214).
 """
+import bisect
 import errno
 import fcntl
+import itertools
 import json
 import logging
 import os
@@ -46,7 +55,7 @@ import uuid
 import numpy as np
 
 from . import filters
-from ._lib import RFX_EBUSY, RfxError, RfxTransientError
+from ._lib import ESIZE, RFX_EBUSY, RfxError, RfxTransientError
 from .index import DeviceIndex
 
 log = logging.getLogger("rfx.store")
@@ -54,6 +63,53 @@ log = logging.getLogger("rfx.store")
 STORE_PREFIX = "fileSearchStores/"  # accepted by routes/stores.py:46 (prefix check)
 FORMAT = 2
 _CENT_MAGIC = b"RFXCENT1"
+DATA_FILES = ("rows.rfx", "meta.jsonl", "files.jsonl", "tombs.bin")
+_ROWS_HDR = 64  # bytes of the row file's header (rfx_rows_append)
+
+
+def compact_policy():
+    """RFX_COMPACT=0 (default: never on its own) | auto: delete_file compacts after its commit when the dead
+    rows are at least RFX_COMPACT_MIN_ROWS (default 65,536: the store size from which the project thinks
+    extra machinery pays, as RFX_SCREEN_MIN_ROWS) AND at least RFX_COMPACT_MIN_FRACTION of the rows (default
+    0.25; DESIGN §4.12 derives it).  Read at every delete: services and tests may change it."""
+    mode = os.environ.get("RFX_COMPACT", "0").strip().lower()
+    return (mode == "auto", int(os.environ.get("RFX_COMPACT_MIN_ROWS", "65536")),
+            float(os.environ.get("RFX_COMPACT_MIN_FRACTION", "0.25")))
+
+
+def _join_ranges(ranges):
+    """(first, count) ranges sorted by first, touching ones joined."""
+    out = []
+    for first, n in sorted(ranges):
+        if out and out[-1][0] + out[-1][1] == first:
+            out[-1] = (out[-1][0], out[-1][1] + n)
+        else:
+            out.append((first, n))
+    return out
+
+
+def _copy_bytes(src_fd, dst_fd, start, n, block=8 << 20):
+    """Append bytes [start, start + n) of src to dst (both positioned by the caller for dst)."""
+    while n > 0:
+        b = os.pread(src_fd, min(n, block), start)
+        if not b:
+            raise OSError(errno.EIO, f"row file ends before byte {start + n}")
+        view = memoryview(b)
+        while view:
+            view = view[os.write(dst_fd, view):]
+        start += len(b)
+        n -= len(b)
+
+
+def _write_file(path, data: bytes):
+    fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC | os.O_CLOEXEC, 0o644)
+    try:
+        view = memoryview(data)
+        while view:
+            view = view[os.write(fd, view):]
+        os.fsync(fd)
+    finally:
+        os.close(fd)
 
 
 def index_spec_from_env():
@@ -143,9 +199,20 @@ class LocalStore:
         self.ivf_meta = None  # committed {"id", "rows"} of the current centroids
         self.ivf = None       # this process's IvfIndex over the committed rows
         self.ivf_id = None
+        self.data_dir = None   # "g-<generation>" after a compaction (manifest "data_dir")
+        self.compacted = None  # the manifest's "compacted" record of this generation
+        # rows move only in a compaction: _moves is odd while one renumbers this object's rows and even
+        # otherwise (numbering()); _prev = the kept ranges of the last one, for hits still in flight
+        self._moves = 0
+        self._prev = None
+        self.on_compact = []  # callbacks(store name) before this object's rows are renumbered
 
     # ---- files -------------------------------------------------------------------------------
     def _p(self, name):
+        """Path of a store file: the four data files live in the generation's data directory (the store
+        directory itself until the first compaction); .lock, the manifest and the centroid files stay put."""
+        if self.data_dir and name in DATA_FILES:
+            return os.path.join(self.path, self.data_dir, name)
         return os.path.join(self.path, name)
 
     def _read_manifest(self):
@@ -159,11 +226,15 @@ class LocalStore:
             raise RuntimeError(f"{self.path}: store format {man.get('format')} != {FORMAT}")
         return man, (st.st_ino, st.st_mtime_ns, st.st_size)
 
-    def _write_manifest(self):
+    def _write_manifest(self, **over):
+        """The commit point.  `over`: fields of a state this object has not adopted yet (compact())."""
         man = {"format": FORMAT, "name": self.name, "display_name": self.display_name, "dim": self.dim,
                "dtype": self.dtype, "generation": self.generation, "version": self.version,
                "rows": len(self.rows), "meta_bytes": self.meta_bytes, "files_bytes": self.files_bytes,
                "tombs": self.tombs, "index": self.spec, "ivf": self.ivf_meta}
+        if self.data_dir:  # (a store that was never compacted has neither key: its files are where they were)
+            man["data_dir"], man["compacted"] = self.data_dir, self.compacted
+        man.update(over)
         tmp = self._p(f"manifest.json.{os.getpid()}.{threading.get_ident()}.tmp")
         with open(tmp, "w", encoding="utf-8") as f:
             json.dump(man, f)
@@ -241,16 +312,42 @@ class LocalStore:
         self._masks = {}
         self._ranges = {}
         self._screen_on = False
+        self.data_dir, self.compacted = man.get("data_dir"), man.get("compacted")
+        self._prev = None  # (a reload keeps no map from the rows it dropped)
 
     def _sync(self, man=None, stat=None):
         """Catch up with the committed state on disk (caller holds self.lock).  Incremental: only
-        what was appended since the last sync is read."""
+        what was appended since the last sync is read.  A compaction by another process removes the
+        generation this one may be reading: on an OSError the manifest is read again, and when it names
+        another generation the catch-up runs once more against that one."""
         if man is None:
             man, stat = self._read_manifest()
         if man is None:
             raise StoreGone(self.path)
+        try:
+            return self._sync_to(man, stat)
+        except OSError:
+            man2, stat2 = self._read_manifest()
+            if man2 is None:
+                raise StoreGone(self.path)
+            if man2["generation"] == man["generation"]:
+                raise
+            self.generation = None  # whatever was half read belongs to a generation that is gone
+        return self._sync_to(man2, stat2)
+
+    def _sync_to(self, man, stat):
         if man["generation"] != self.generation:
-            self._reset(man)
+            c = man.get("compacted")
+            if c and self.index is not None and hasattr(self.index, "compact") \
+                    and c["from_generation"] == self.generation and c["from_version"] == self.version \
+                    and c["rows_before"] == len(self.rows) and self._follow_compaction(man, c):
+                # this object held exactly the state that was compacted: the same ranges, on the device
+                if man["version"] == self.version:
+                    self.ivf_meta = man.get("ivf")
+                    self._ivf_catch_up()
+                    self._maybe_screen()
+            else:
+                self._reset(man)
         if man["version"] == self.version:
             self._stat = stat
             return
@@ -306,6 +403,7 @@ class LocalStore:
     def add_document(self, chunks, vecs, display_name, metadata=None):
         with self.lock, self._WriterLock(self):
             self._sync()  # append at the end of what every writer committed
+            self._gc_generations()
             file_id = f"files/local-{uuid.uuid4().hex}"
             first = self.index.rows
             # everything after the catch-up is one commit: any failure (ENOSPC, EIO, interrupt) in
@@ -337,6 +435,200 @@ class LocalStore:
         man, stat = self._read_manifest()
         self.generation = None
         self._sync(man, stat)
+
+    # ---- compaction: reclaim the rows of deleted documents ---------------------------------
+    def dead_rows(self) -> int:
+        """Rows of deleted documents this store still holds (on disk, in device memory, in every scan)."""
+        with self.lock:
+            return len(self.rows) - sum(f["n"] for f in self.files.values() if not f["deleted"])
+
+    def dead_fraction(self) -> float:
+        with self.lock:
+            return self.dead_rows() / len(self.rows) if self.rows else 0.0
+
+    def _keep_ranges(self):
+        """The live files' row ranges, ascending, touching ones joined: what a compaction keeps."""
+        return _join_ranges((f["first"], f["n"]) for f in self.files.values() if not f["deleted"] and f["n"])
+
+    def _gc_generations(self):
+        """Writer, under the writer lock, after the catch-up: remove what no manifest names any more — the
+        g-* directories of crashed compactions and of generations that were compacted away, and the store
+        directory's own data files once a data directory is in force."""
+        for name in os.listdir(self.path):
+            if name.startswith("g-") and name != self.data_dir:
+                shutil.rmtree(os.path.join(self.path, name), ignore_errors=True)
+            elif name in DATA_FILES and self.data_dir:
+                try:
+                    os.unlink(os.path.join(self.path, name))
+                except OSError:
+                    pass
+
+    def _compacted_state(self, ranges, encode=True):
+        """(rows, files, metadata bytes, file-record bytes) of this object's state with only `ranges` kept:
+        the live rows' metadata lines and one add record per live file with its new first row.  The writer
+        writes the bytes; a reader that follows the compaction on the device adopts the same rows and files
+        (encode=False: no bytes; their lengths are in the manifest's "compacted" record)."""
+        starts, pos = [], 0
+        for first, n in ranges:
+            starts.append((first, pos))
+            pos += n
+        firsts = [s[0] for s in starts]
+
+        def moved(row):  # kept rows before `row` = the new id of a kept row
+            i = bisect.bisect_right(firsts, row) - 1
+            if i < 0:
+                return 0
+            return starts[i][1] + min(row - starts[i][0], ranges[i][1])
+
+        rows = [rc for first, n in ranges for rc in self.rows[first:first + n]]
+        files, recs = {}, []
+        for fid, f in self.files.items():
+            if f["deleted"]:
+                continue
+            rec = {"op": "add", "id": fid, "first": moved(f["first"]), "n": f["n"], "display_name": f["display_name"],
+                   "uri": f["uri"], "metadata": f.get("metadata")}
+            if encode:
+                recs.append(json.dumps(rec) + "\n")
+            files[fid] = {"first": rec["first"], "n": f["n"], "display_name": f["display_name"], "uri": f["uri"],
+                          "deleted": False, "metadata": f.get("metadata")}
+        if not encode:
+            return rows, files, None, None
+        meta = "".join(json.dumps({"f": fid, "t": t}, ensure_ascii=False) + "\n" for fid, t in rows)
+        return rows, files, meta.encode(), "".join(recs).encode()
+
+    def _write_generation(self, data_dir, ranges, meta, recs):
+        """The data files of a new generation in <store>/<data_dir>/, each fsync'ed, then the directory.
+        rows.rfx = the header and the kept byte ranges of the current row file, copied on the host."""
+        d = os.path.join(self.path, data_dir)
+        os.mkdir(d)
+        if ranges:
+            rb = self.dim * ESIZE[self.dtype]
+            src = os.open(self._p("rows.rfx"), os.O_RDONLY | os.O_CLOEXEC)
+            try:
+                dst = os.open(os.path.join(d, "rows.rfx"), os.O_WRONLY | os.O_CREAT | os.O_EXCL | os.O_CLOEXEC, 0o644)
+                try:
+                    _copy_bytes(src, dst, 0, _ROWS_HDR)
+                    for first, n in ranges:
+                        _copy_bytes(src, dst, _ROWS_HDR + first * rb, n * rb)
+                    os.fsync(dst)
+                finally:
+                    os.close(dst)
+            finally:
+                os.close(src)
+        _write_file(os.path.join(d, "meta.jsonl"), meta)
+        _write_file(os.path.join(d, "files.jsonl"), recs)
+        _write_file(os.path.join(d, "tombs.bin"), b"")
+        _fsync_dir(d)
+        _fsync_dir(self.path)
+
+    def _adopt_compaction(self, ranges, state, generation, version, data_dir, compacted):
+        """Renumber this object's rows: the device index keeps `ranges` (no row bytes are read back from
+        disk) or, without a compact() (a sharded index, host stand-ins), is reloaded from the new files."""
+        rows, files = state[:2]
+        for cb in list(self.on_compact):  # union views over this store pin the allocation about to be freed
+            cb(self.name)
+        self._moves += 1  # odd: searches of this object wait (numbering)
+        try:
+            # (firsts / pos: each range's first old row and first new row, for row_info's bisect)
+            prev = {"generation": self.generation, "ranges": ranges, "firsts": [f for f, _ in ranges],
+                    "pos": list(itertools.accumulate((n for _, n in ranges), initial=0))}
+            self.generation, self.version = generation, version
+            self.data_dir, self.compacted = data_dir, compacted
+            self.rows, self.files = rows, files
+            self.meta_bytes, self.files_bytes, self.tombs = compacted["meta_bytes"], compacted["files_bytes"], 0
+            self._masks, self._ranges = {}, {}
+            if self._screen_on is None:
+                self._screen_on = False  # declined for the old generation: this one may fit
+            if hasattr(self.index, "compact"):
+                kept = self.index.compact(ranges)
+                if kept != len(rows):
+                    raise RuntimeError(f"{self.path}: the index kept {kept} rows, the store {len(rows)}")
+            else:
+                self.index.close()
+                self.index = self.index_factory(self.dim, self.dtype, self.device)
+                self._screen_on = False
+                if rows:
+                    self.index.rows_sync(self._p("rows.rfx"), len(rows))
+            self._prev = prev
+            self._drop_ivf()  # the lists hold old row ids; the centroids (ivf_meta, ivf-*.bin) do not
+        finally:
+            self._moves += 1
+
+    def compact(self):
+        """Rewrite the store without the rows of deleted documents: a new generation on disk (data files in
+        g-<generation>/, one atomic manifest as the commit point), the device rows gathered into a smaller
+        allocation.  Row ids change (row_info translates hits of the generation before).  Returns
+        {"rows_before", "rows", "seconds"}; nothing is committed when no row is dead."""
+        t0 = time.monotonic()
+        with self.lock, self._WriterLock(self):
+            self._sync()
+            self._gc_generations()
+            out = self._compact_locked()
+        out["seconds"] = time.monotonic() - t0
+        return out
+
+    def _compact_locked(self):
+        ranges = self._keep_ranges()
+        before = len(self.rows)
+        kept = sum(n for _, n in ranges)
+        if kept == before:
+            return {"rows_before": before, "rows": before}
+        generation = uuid.uuid4().hex
+        data_dir = f"g-{generation}"
+        state = self._compacted_state(ranges)
+        compacted = {"from_generation": self.generation, "from_version": self.version, "rows_before": before,
+                     "rows": kept, "meta_bytes": len(state[2]), "files_bytes": len(state[3])}
+        try:  # nothing of this object or of the committed generation is touched before the commit
+            self._write_generation(data_dir, ranges, state[2], state[3])
+            self._write_manifest(generation=generation, version=self.version + 1, rows=kept, meta_bytes=len(state[2]),
+                                 files_bytes=len(state[3]), tombs=0, data_dir=data_dir, compacted=compacted)
+        except BaseException:
+            try:
+                committed = (self._read_manifest()[0] or {}).get("generation") == generation
+            except Exception:
+                committed = None  # unknown: leave the directory to the next writer's clean-up
+            if committed:  # the rename happened and something after it failed: the new generation is in force
+                self._rollback(None)
+            elif committed is False:
+                shutil.rmtree(os.path.join(self.path, data_dir), ignore_errors=True)
+            raise
+        try:
+            self._adopt_compaction(ranges, state, generation, self.version + 1, data_dir, compacted)
+        except BaseException:
+            self._rollback(None)  # committed: re-open from the new generation's files
+            raise
+        self._gc_generations()  # the old generation's data files
+        self._ivf_catch_up()
+        self._maybe_screen()
+        return {"rows_before": before, "rows": kept}
+
+    def _follow_compaction(self, man, c):
+        """Reader: the manifest's compaction started from exactly this object's state, so the same ranges
+        applied to its index give the committed rows; no row bytes are read from disk."""
+        ranges = self._keep_ranges()
+        state = self._compacted_state(ranges, encode=False)
+        if len(state[0]) != c["rows"] or "meta_bytes" not in c or "files_bytes" not in c:
+            return False  # not the state the writer had after all: reload
+        try:
+            self._adopt_compaction(ranges, state, man["generation"], c["from_version"] + 1, man.get("data_dir"), c)
+        except BaseException:
+            self.generation = None  # the next catch-up reloads
+            raise
+        return True
+
+    def numbering(self):
+        """(token, generation) of this object's row numbering, for code that resolves rows, masks or ranges
+        around a search: when numbering_changed(token) is true afterwards, a compaction renumbered the rows
+        meanwhile and the work is done again.  Waits while a compaction is moving the rows."""
+        while True:
+            seq = self._moves
+            if seq & 1:
+                with self.lock:
+                    continue
+            return seq, self.generation
+
+    def numbering_changed(self, token) -> bool:
+        return self._moves != token
 
     # ---- IVF (config 5) ------------------------------------------------------------------------------
     def _ivf_enabled(self):
@@ -459,6 +751,7 @@ class LocalStore:
     def delete_file(self, file_id) -> bool:
         with self.lock, self._WriterLock(self):
             self._sync()
+            self._gc_generations()
             f = self.files.get(file_id)
             if not f or f["deleted"]:
                 return False
@@ -476,7 +769,23 @@ class LocalStore:
             except BaseException:
                 self._rollback(None)
                 raise
+            self._auto_compact()
             return True
+
+    def _auto_compact(self):
+        """RFX_COMPACT=auto (compact_policy): after a delete's own commit, inside the same writer-lock hold.
+        A compaction that fails is logged; the delete has succeeded either way."""
+        auto, min_rows, min_fraction = compact_policy()
+        if not auto:
+            return
+        dead = self.dead_rows()
+        if dead == 0 or dead < min_rows or dead < min_fraction * len(self.rows):
+            return
+        try:
+            out = self._compact_locked()
+            log.info("store %s: compacted %d -> %d rows", self.name, out["rows_before"], out["rows"])
+        except Exception as e:
+            log.warning("store %s: compaction after a delete failed (%s); the rows stay tombstoned", self.name, e)
 
     # ---- reads -------------------------------------------------------------------------------------
     def tomb_rows(self, start: int, end: int = None) -> np.ndarray:
@@ -486,6 +795,16 @@ class LocalStore:
         if end <= start:
             return np.zeros(0, dtype=np.int64)
         return np.frombuffer(_read_range(self._p("tombs.bin"), 8 * start, 8 * end), dtype="<i8").astype(np.int64)
+
+    def search_gen(self, queries, k):
+        """search() plus the generation whose row numbering the answer uses (row_info's argument): a
+        compaction that renumbers the rows while the search runs makes it run again.  Unfiltered only: a
+        caller that resolves a mask or ranges first brackets that work with numbering() itself."""
+        while True:
+            token, generation = self.numbering()
+            s, r = self.search(queries, k)
+            if not self.numbering_changed(token):
+                return s, r, generation
 
     def search(self, queries, k, row_mask=None):
         """(scores, rows) of the top-k rows per query.  An IVF store with trained lists answers
@@ -546,9 +865,27 @@ class LocalStore:
                 self._ranges[key] = out
             return self._ranges[key]
 
-    def row_info(self, row):
+    def row_info(self, row, generation=None):
         """(file_id, chunk text, title, uri) of a row, or None for a row this process has no
-        metadata for (cannot happen after a consistent sync; guarded anyway)."""
+        metadata for (cannot happen after a consistent sync; guarded anyway).  generation: the one the
+        search that returned `row` ran under (numbering / search_gen; None = the current one).  A row of the
+        generation just before the last compaction is translated through its kept ranges (None when it was
+        deleted); rows of any older generation are unknown: None."""
+        while True:  # one numbering throughout: a compaction swaps generation, _prev, rows and files one by one
+            token, current = self.numbering()
+            out = self._row_info(row, generation, current)
+            if not self.numbering_changed(token):
+                return out
+
+    def _row_info(self, row, generation, current):
+        if generation is not None and generation != current:
+            prev = self._prev
+            if prev is None or prev["generation"] != generation or row < 0:
+                return None
+            i = bisect.bisect_right(prev["firsts"], row) - 1
+            if i < 0 or row >= prev["firsts"][i] + prev["ranges"][i][1]:
+                return None
+            row = prev["pos"][i] + row - prev["firsts"][i]
         if not 0 <= row < len(self.rows):
             return None
         fid, text = self.rows[row]
@@ -595,9 +932,16 @@ class StoreRegistry:
         os.makedirs(self.root, exist_ok=True)
         st = LocalStore.create(self._dir(name), name, display_name, dim, dtype, self.device, self.index_factory,
                                spec if spec is not None else index_spec_from_env(), self.ivf_factory)
+        st.on_compact.append(self._compacted)
         with self._lock:
             self._stores[name] = st
         return st
+
+    def _compacted(self, name):
+        """A store of this registry is about to renumber its rows: what was built over the old numbering
+        (batchers' cached masks aside, the union views that pin its allocation) goes, as on eviction."""
+        for cb in self.on_evict:
+            cb(name)
 
     def _evict(self, name):
         st = self._stores.pop(name, None)
@@ -623,6 +967,7 @@ class StoreRegistry:
                 st = LocalStore.open(d, self.device, self.index_factory, self.ivf_factory)
             except StoreGone:
                 return None
+            st.on_compact.append(self._compacted)
             self._stores[name] = st
             return st
 
