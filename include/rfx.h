@@ -209,6 +209,30 @@ int rfx_segmented_plan(int64_t rows, int dim, int dtype, int64_t nq, int k, int 
                        const int64_t* group_r_h, const int64_t* ranges_h, int64_t* items_h /* [cap][4]: group,
                        first query, first selected-row position, selected rows */, int64_t cap, int64_t* out_n_items,
                        int* out_lists_per_query);
+/* Diversified retrieval: greedy MMR (maximal marginal relevance) selection of k of the
+ * n_cand best rows of a search, one launch for the batch.  The stage after the retrieval slice of ask_stream
+ * (gemini_rag.py:517-551): overlapping chunk windows and re-uploaded files make the k best chunks near-copies
+ * of each other.  Input per query: cand_scores_d / cand_rows_d [nq][n_cand_max], the answer of any rfx_search*
+ * at k = n_cand_max on this index (score desc, row asc), of which the first n_cand_h[q] entries are used.
+ * Entries with a row outside [0, rows), and entries whose stored row holds a NaN (tombstoned), are padding.
+ *   sim(i, j) = fl32 of the f64 sum of the exact products of stored rows i and j (the score rule, on two rows);
+ *   step 0 picks the first valid candidate; step t >= 1 picks the unpicked valid candidate that maximises, in
+ *   f64 with every operation rounded on its own, L * s_i - (1 - L) * max over picked j of sim(i, j), L =
+ *   lambda_h[q]; ties go to the lower candidate position.
+ * Output [nq][k]: the picks in pick order, each with its own score and row, then (-inf, -1); out_obj_d (may be
+ * NULL) the objectives as f32 (step 0: L * s).  lambda = 1 returns the first k valid candidates; the first k'
+ * picks of a selection to k are the selection to k'.  queries_d is not read (the candidates carry the scores).
+ * Stream-ordered after the search that wrote the candidates; the host arrays may be freed on return (staged as
+ * rfx_search_segmented stages its tables).  RFX_EINVAL before anything is enqueued: k or n_cand_max outside
+ * 1..64, k > n_cand_max, nq outside 1..1024, a lambda outside [0, 1] or NaN, an n_cand_h entry outside
+ * 1..n_cand_max, a workspace under rfx_mmr_workspace_bytes.  Any handle rfx_search_masked accepts, union
+ * views included; IVF handles are not index handles. */
+int rfx_mmr_workspace_bytes(rfx_index_t h, int64_t nq, int n_cand_max, size_t* out_bytes);
+int rfx_mmr_select(rfx_index_t h, const void* queries_d, int64_t nq, int n_cand_max, int k,
+                   const float* lambda_h, const int32_t* n_cand_h,      /* [nq] host; NULL = 0.5 / n_cand_max */
+                   const float* cand_scores_d, const int64_t* cand_rows_d, /* [nq][n_cand_max] */
+                   float* out_scores_d, int64_t* out_rows_d, float* out_obj_d /* may be NULL */,
+                   void* ws_d, size_t ws_bytes, void* stream);
 /* Merge per-query candidate lists into the final top-k.  rows are int32 (rows_are_i64 = 0) or
  * int64 (1); row_offset is added to every returned row (shard base for multi-GPU). */
 int rfx_topk_merge(const float* cand_scores_d, const void* cand_rows_d, int rows_are_i64,

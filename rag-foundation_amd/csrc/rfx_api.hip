@@ -34,6 +34,7 @@
 #include <vector>
 
 #include "k_compact.h"
+#include "k_mmr.h"
 #include "rfx_kernels.h"
 
 namespace {
@@ -2502,6 +2503,102 @@ int rfx_index_compact_times(rfx_index_t h, double* out_ms) {
   if (!ix || !out_ms) return fail(RFX_EINVAL, "unknown index handle / null out");
   RFX_RLOCK(ix);
   std::copy(ix->compact_ms, ix->compact_ms + 5, out_ms);
+  return RFX_OK;
+}
+
+}  // extern "C"
+
+// ---- diversified retrieval: MMR selection over the top candidates of a search ----------------
+// (the stage after the retrieval slice of ask_stream, gemini_rag.py:517-551; kernel: k_mmr.h)
+namespace {
+struct MmrLayout {
+  size_t ncand_off, total;  // the lambdas sit at offset 0
+};
+MmrLayout mmr_layout(int64_t nq) {
+  MmrLayout L;
+  L.ncand_off = align_up((size_t)nq * sizeof(float));
+  L.total = L.ncand_off + align_up((size_t)nq * sizeof(int32_t));
+  return L;
+}
+int mmr_check_shape(int64_t nq, int n_cand_max, int k) {
+  if (n_cand_max < 1 || n_cand_max > rfx::kMmrMaxCand)
+    return fail(RFX_EINVAL, "n_cand_max=%d out of range [1, %d]", n_cand_max, rfx::kMmrMaxCand);
+  if (k < 1 || k > rfx::kMmrMaxCand) return fail(RFX_EINVAL, "k=%d out of range [1, %d]", k, rfx::kMmrMaxCand);
+  if (k > n_cand_max) return fail(RFX_EINVAL, "k=%d > n_cand_max=%d", k, n_cand_max);
+  if (nq < 1 || nq > rfx::kMmrMaxNq)
+    return fail(RFX_EINVAL, "nq=%lld out of [1, %d]", (long long)nq, rfx::kMmrMaxNq);
+  return RFX_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int rfx_mmr_workspace_bytes(rfx_index_t h, int64_t nq, int n_cand_max, size_t* out_bytes) {
+  auto ix = get(h);
+  if (!ix) return fail(RFX_EINVAL, "unknown index handle");
+  if (!out_bytes) return fail(RFX_EINVAL, "null output");
+  if (const int rc = mmr_check_shape(nq, n_cand_max, 1)) return rc;
+  *out_bytes = mmr_layout(nq).total;
+  return RFX_OK;
+}
+
+int rfx_mmr_select(rfx_index_t h, const void* queries_d, int64_t nq, int n_cand_max, int k, const float* lambda_h,
+                   const int32_t* n_cand_h, const float* cand_scores_d, const int64_t* cand_rows_d,
+                   float* out_scores_d, int64_t* out_rows_d, float* out_obj_d, void* ws_d, size_t ws_bytes,
+                   void* stream) {
+  (void)queries_d;  // the candidates carry their scores: the queries are not read again
+  auto ix = get(h);
+  if (!ix) return fail(RFX_EINVAL, "unknown index handle");
+  RFX_RLOCK(ix);  // the data pointer moves on growth
+  if (const int rc = mmr_check_shape(nq, n_cand_max, k)) return rc;
+  if (lambda_h)
+    for (int64_t q = 0; q < nq; ++q)
+      if (!(lambda_h[q] >= 0.0f && lambda_h[q] <= 1.0f))  // (a NaN fails both compares)
+        return fail(RFX_EINVAL, "lambda[%lld]=%g outside [0, 1]", (long long)q, (double)lambda_h[q]);
+  if (n_cand_h)
+    for (int64_t q = 0; q < nq; ++q)
+      if (n_cand_h[q] < 1 || n_cand_h[q] > n_cand_max)
+        return fail(RFX_EINVAL, "n_cand[%lld]=%d outside [1, %d]", (long long)q, (int)n_cand_h[q], n_cand_max);
+  if (!cand_scores_d || !cand_rows_d || !out_scores_d || !out_rows_d) return fail(RFX_EINVAL, "null candidates / outputs");
+  const MmrLayout L = mmr_layout(nq);
+  if (ws_bytes < L.total || !ws_d) return fail(RFX_EINVAL, "workspace too small (%zu < %zu)", ws_bytes, L.total);
+  if (ix->dim % 64 != 0 || (size_t)ix->dim * 8 > rfx::kMmrLdsBudget)
+    return fail(RFX_EUNSUPPORTED, "mmr select: dim %d unsupported", ix->dim);
+  RFX_HIP(hipSetDevice(ix->device));
+  hipStream_t st = (hipStream_t)stream;
+  uint8_t* ws = (uint8_t*)ws_d;
+  {
+    // The per-query tables through the index's pinned staging buffer, as rfx_search_segmented stages its
+    // tables: the caller's arrays may die on return, and the copy stays stream-ordered.
+    std::lock_guard<std::mutex> slk(ix->seg_mu);
+    if (!ix->seg_ev) RFX_HIP(hipEventCreateWithFlags(&ix->seg_ev, hipEventDisableTiming));
+    else RFX_HIP(hipEventSynchronize(ix->seg_ev));
+    const size_t need = L.total;
+    if (ix->seg_stage_bytes < need) {
+      if (ix->seg_stage) RFX_HIP(hipHostFree(ix->seg_stage));
+      ix->seg_stage = nullptr;
+      ix->seg_stage_bytes = 0;
+      const size_t want = std::max(need * 2, (size_t)1 << 16);
+      if (hipHostMalloc(&ix->seg_stage, want, hipHostMallocDefault) != hipSuccess)
+        return fail(RFX_ENOMEM, "hipHostMalloc(%zu) failed (mmr select tables)", want);
+      ix->seg_stage_bytes = want;
+    }
+    uint8_t* stage = (uint8_t*)ix->seg_stage;
+    float* lam_s = (float*)stage;
+    int32_t* nc_s = (int32_t*)(stage + L.ncand_off);
+    for (int64_t q = 0; q < nq; ++q) {
+      lam_s[q] = lambda_h ? lambda_h[q] : 0.5f;
+      nc_s[q] = n_cand_h ? n_cand_h[q] : n_cand_max;
+    }
+    // one copy: both tables, with the gap between them
+    RFX_HIP(hipMemcpyAsync(ws, stage, L.ncand_off + (size_t)nq * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    RFX_HIP(hipEventRecord(ix->seg_ev, st));
+  }
+  if (rfx::launch_mmr_select(ix->data, ix->data ? ix->rows : 0, ix->dim, ix->dtype, nq, n_cand_max, k, (const float*)ws,
+                             (const int*)(ws + L.ncand_off), cand_scores_d, cand_rows_d, out_scores_d, out_rows_d,
+                             out_obj_d, st) != 0)
+    return fail(RFX_EUNSUPPORTED, "mmr select launch rejected");
+  RFX_HIP(hipGetLastError());
   return RFX_OK;
 }
 

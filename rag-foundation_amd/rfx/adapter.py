@@ -96,6 +96,10 @@ class LocalGpuRag:
         # metadata filters become row masks; RFX_METADATA_FILTER=0 ignores them
         # like the reference mock (gemini_rag.py:673-694)
         self.apply_filters = os.environ.get("RFX_METADATA_FILTER", "1") != "0"
+        # diversified retrieval (MMR over the top candidates): RFX_MMR_LAMBDA is the default
+        # lambda of every question; unset = off (the k best chunks as they come)
+        lam = os.environ.get("RFX_MMR_LAMBDA", "").strip()
+        self.diversity = float(lam) if lam else None
         self.is_mock = True
 
     # -------- Stores --------
@@ -146,26 +150,32 @@ class LocalGpuRag:
 
     # -------- Query (sync & stream) --------
     def retrieve(self, question: str, store_names: Sequence[str], k: Optional[int] = None,
-                 metadata_filter: Optional[Any] = None):
+                 metadata_filter: Optional[Any] = None, diversity: Optional[Any] = None):
         """Top-k hits.  k: the request's top_k (the reference route drops it,
-        chat.py:66), default self.top_k; 1..64."""
+        chat.py:66), default self.top_k; 1..64.  diversity: a lambda in [0, 1] or {"lambda": ..,
+        "fetch_k": ..} picks the k hits by MMR from the fetch_k best (GpuRetriever.search); None = the
+        default of RFX_MMR_LAMBDA (unset: off)."""
         filt = metadata_filter if self.apply_filters else None
+        div = self.diversity if diversity is None else diversity
+        if div is None:
+            return self.retriever.search(list(store_names or []), question, self.top_k if k is None else int(k),
+                                         metadata_filter=filt)
         return self.retriever.search(list(store_names or []), question, self.top_k if k is None else int(k),
-                                     metadata_filter=filt)
+                                     metadata_filter=filt, diversity=div)
 
     def ask(self, *, contents: Any, store_names: Sequence[str], metadata_filter: Optional[Any], model: str,
-            system: Optional[str] = None, top_k: Optional[int] = None) -> Any:
+            system: Optional[str] = None, top_k: Optional[int] = None, diversity: Optional[Any] = None) -> Any:
         with observe("generate"):
-            hits = self.retrieve(contents_to_text(contents), store_names, top_k, metadata_filter)
+            hits = self.retrieve(contents_to_text(contents), store_names, top_k, metadata_filter, diversity)
             return build_response(hits, store_names)
 
     def ask_stream(self, *, contents: Any, store_names: Sequence[str], metadata_filter: Optional[Any], model: str,
-                   system: Optional[str] = None, top_k: Optional[int] = None):
+                   system: Optional[str] = None, top_k: Optional[int] = None, diversity: Optional[Any] = None):
         """The reference's keyword set plus an optional top_k (callers that do not pass it get
         self.top_k, so the reference call site chat.py:499-505 works unchanged)."""
         with observe("generate_stream"):
             text = contents_to_text(contents)
-            resp = build_response(self.retrieve(text, store_names, top_k, metadata_filter), store_names)
+            resp = build_response(self.retrieve(text, store_names, top_k, metadata_filter, diversity), store_names)
         yield SimpleNamespace(text=f"[mock-mode] {text or 'response'}", candidates=None,
                               usage_metadata=SimpleNamespace(prompt_token_count=0, candidates_token_count=0))
         yield resp

@@ -241,6 +241,52 @@ class DeviceIndex:
         inv[order] = torch.arange(nq, dtype=torch.int64, device=dev)
         return out_s.index_select(0, inv), out_r.index_select(0, inv)
 
+    # ---- diversified retrieval (MMR over the top candidates) ----------------------------
+    def mmr_workspace_bytes(self, nq: int, n_cand_max: int) -> int:
+        b = ctypes.c_size_t()
+        check(lib.rfx_mmr_workspace_bytes(self.handle, int(nq), int(n_cand_max), ctypes.byref(b)))
+        return b.value
+
+    def mmr_select(self, queries: torch.Tensor, scores: torch.Tensor, rows: torch.Tensor, k: int, lam=0.5,
+                   n_cand=None, workspace: torch.Tensor = None, stream=None, return_objective: bool = False):
+        """Greedy MMR selection (rfx_mmr_select) of k of each query's candidates: (scores f32, rows int64)
+        [nq][n_cand_max] as a search at k = n_cand_max returns them.  lam: one float or [nq] floats in
+        [0, 1] (1 = relevance only); n_cand: None, an int, or [nq] ints in 1..n_cand_max = how many of its
+        candidates a query uses.  Returns (scores [nq][k], rows [nq][k]) in pick order, padded (-inf, -1),
+        and the objectives [nq][k] f32 with return_objective."""
+        import numpy as np
+        q = self._check_queries(queries)
+        nq = q.shape[0]
+        dev = q.device
+        if scores.shape != rows.shape or scores.dim() != 2 or scores.shape[0] != nq:
+            raise ValueError(f"candidates must be [nq={nq}][n_cand] scores and rows of equal shape")
+        if scores.dtype != torch.float32 or rows.dtype != torch.int64 or scores.device != dev or rows.device != dev:
+            raise ValueError("candidates must be (float32, int64) tensors on the queries' device")
+        cs, cr = scores.contiguous(), rows.contiguous()
+        n_max = cs.shape[1]
+        lam_a = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=np.float32), (nq,)))
+        nc_a = None if n_cand is None else \
+            np.ascontiguousarray(np.broadcast_to(np.asarray(n_cand, dtype=np.int32), (nq,)))
+        out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        out_o = torch.empty((nq, k), dtype=torch.float32, device=dev) if return_objective else None
+        need = self.mmr_workspace_bytes(nq, n_max)
+        ws = workspace if workspace is not None and workspace.numel() >= need else \
+            torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.rfx_mmr_select(self.handle, ptr(q), nq, int(n_max), int(k), lam_a.ctypes.data,
+                                     nc_a.ctypes.data if nc_a is not None else None, ptr(cs), ptr(cr), ptr(out_s),
+                                     ptr(out_r), ptr(out_o) if out_o is not None else None, ptr(ws), ws.numel(),
+                                     stream_ptr(stream)))
+        return (out_s, out_r, out_o) if return_objective else (out_s, out_r)
+
+    def search_mmr(self, queries: torch.Tensor, k: int, fetch_k: int, lam=0.5, row_mask: torch.Tensor = None):
+        """The search at fetch_k, then the MMR selection of k of its answer."""
+        if not 1 <= k <= fetch_k <= 64:
+            raise ValueError(f"need 1 <= k <= fetch_k <= 64, got k={k} fetch_k={fetch_k}")
+        s, r = self.search(queries, int(fetch_k), row_mask=row_mask)
+        return self.mmr_select(queries, s, r, int(k), lam=lam)
+
     def search_records(self, queries: torch.Tensor, k: int, row_offset: int = 0, out: torch.Tensor = None,
                        workspace: torch.Tensor = None, stream=None, row_mask: torch.Tensor = None) -> torch.Tensor:
         """The search as [nq][k][2] int64 merge records (score bits, row + row_offset): one shard's

@@ -73,6 +73,54 @@ def segmented_max_fraction() -> float:
     return float(os.environ.get("RFX_SEGMENTED_MAX_FRACTION", "0.5"))
 
 
+DIVERSITY_ERROR = "diversity needs a flat single-device store"
+
+
+def default_fetch_k(k: int) -> int:
+    """Candidates a diversified question fetches when it names no fetch_k: min(64, max(4k, 16))."""
+    return min(64, max(4 * int(k), 16))
+
+
+def parse_diversity(diversity, k: int):
+    """diversity (None | lambda | {"lambda": .., "fetch_k": ..}) -> None or (lambda, fetch_k) with
+    0 <= lambda <= 1 and k <= fetch_k <= 64 (MMR over the fetch_k best rows)."""
+    if diversity is None:
+        return None
+    if isinstance(diversity, dict):
+        unknown = set(diversity) - {"lambda", "fetch_k"}
+        if unknown or "lambda" not in diversity:
+            raise ValueError(f"diversity takes 'lambda' and optionally 'fetch_k', got {sorted(diversity)}")
+        lam, fetch_k = diversity["lambda"], diversity.get("fetch_k")
+    else:
+        lam, fetch_k = diversity, None
+    if isinstance(lam, bool) or not isinstance(lam, (int, float)) or not 0.0 <= float(lam) <= 1.0:
+        raise ValueError(f"diversity lambda={lam!r} must be a number in [0, 1]")
+    fetch_k = default_fetch_k(k) if fetch_k is None else int(fetch_k)
+    if not k <= fetch_k <= 64:
+        raise ValueError(f"diversity fetch_k={fetch_k} must satisfy k={k} <= fetch_k <= 64")
+    return float(lam), fetch_k
+
+
+def _diversity_ok(st) -> bool:
+    """A flat store on one device: its index selects on the device (DeviceIndex.mmr_select) and no IVF
+    lists answer in its place."""
+    return hasattr(st.index, "mmr_select") and getattr(st, "spec", {}).get("kind", "flat") == "flat"
+
+
+def _search_diverse(index, q, items, div_at, row_mask=None):
+    """The batch's search at its largest fetch_k (k for the items that asked for no diversity), then ONE
+    MMR selection over the batch: lambda 1 and n_cand = k for the items without, their own lambda and
+    fetch_k otherwise.  items[i][1] = k, items[i][div_at] (when present) = (lambda, fetch_k).  Returns
+    host lists (scores, rows) [nq][largest k]."""
+    divs = [it[div_at] if len(it) > div_at else None for it in items]
+    ks = [it[1] for it in items]
+    fetch = max(d[1] if d else k for d, k in zip(divs, ks))
+    s, r = index.search(q, fetch, row_mask=row_mask)
+    s, r = index.mmr_select(q, s, r, max(ks), lam=[d[0] if d else 1.0 for d in divs],
+                            n_cand=[d[1] if d else k for d, k in zip(divs, ks)])
+    return s.cpu(), r.cpu()
+
+
 class _StoreAnswer(tuple):
     """(store, scores, rows) of one question, plus .generation: the store generation whose row numbering
     `rows` uses (LocalStore.row_info translates or refuses rows of an earlier one after a compaction)."""
@@ -153,6 +201,7 @@ class GpuRetriever:
         self.union = os.environ.get("RFX_UNION", "1") != "0"
         self.last_path = None  # "union" | "per-store" (tests, diagnostics)
         self.last_filter_path = None  # "segmented" | "masked": how the last filtered batch was searched
+        self.last_diversity = None  # "union" | "store" | None: where the last question was diversified
 
     @property
     def registry(self):
@@ -206,6 +255,14 @@ class GpuRetriever:
     def _search_store_batch(self, st, items, row_mask=None):
         """One GPU search for a batch of (question, k) against one store: one embedding GEMM,
         one scan + merge at the largest k; each item gets its own first k."""
+        if any(len(it) > 2 for it in items):  # some ask for diversity: (question, k, (lambda, fetch_k))
+            if not _diversity_ok(st):
+                raise ValueError(DIVERSITY_ERROR)
+            with torch.cuda.device(st.device):
+                q = self.embedder(st.dim).embed_texts([it[0] for it in items], st.dtype)
+                s, r = _search_diverse(st.index, q, items, 2, row_mask)
+                s, r = s.tolist(), r.tolist()
+            return [(s[i][:it[1]], r[i][:it[1]]) for i, it in enumerate(items)]
         kmax = max(k for _, k in items)
         with torch.cuda.device(st.device):
             q = self.embedder(st.dim).embed_texts([t for t, _ in items], st.dtype)
@@ -247,7 +304,10 @@ class GpuRetriever:
     def _filtered_batch(self, st, items):
         out = [None] * len(items)
         groups = []  # (filter, item indices, ranges) of the filters that select rows
-        for filt, idxs in filters.group_by_filter([f for _, _, f in items]):
+        diverse = any(len(it) > 3 for it in items)  # (question, k, filter, (lambda, fetch_k))
+        if diverse and not _diversity_ok(st):
+            raise ValueError(DIVERSITY_ERROR)
+        for filt, idxs in filters.group_by_filter([it[2] for it in items]):
             ranges = st.segment_ranges(filt)
             if ranges:
                 groups.append((filt, idxs, ranges))
@@ -263,7 +323,7 @@ class GpuRetriever:
                 mask = st.row_mask(filt)
                 if mask is None:
                     continue
-                res = self._search_store_batch(st, [items[i][:2] for i in idxs], mask)
+                res = self._search_store_batch(st, [items[i][:2] + items[i][3:] for i in idxs], mask)
                 for i, (s, r) in zip(idxs, res):
                     out[i] = (st, s, r)
             return out
@@ -271,9 +331,19 @@ class GpuRetriever:
         live = [i for _, idxs, _ in groups for i in idxs]
         pos = {i: p for p, i in enumerate(live)}
         kmax = max(items[i][1] for i in live)
+        if diverse:  # the segmented search at the largest fetch_k, then one selection over the batch
+            divs = [items[i][3] if len(items[i]) > 3 else None for i in live]
+            ks = [items[i][1] for i in live]
+            fetch = max(d[1] if d else k for d, k in zip(divs, ks))
         with torch.cuda.device(st.device):
             q = self.embedder(st.dim).embed_texts([items[i][0] for i in live], st.dtype)
-            s, r = st.index.search_segmented(q, kmax, [([pos[i] for i in idxs], ranges) for _, idxs, ranges in groups])
+            seg = [([pos[i] for i in idxs], ranges) for _, idxs, ranges in groups]
+            if diverse:
+                s, r = st.index.search_segmented(q, fetch, seg)
+                s, r = st.index.mmr_select(q, s, r, kmax, lam=[d[0] if d else 1.0 for d in divs],
+                                           n_cand=[d[1] if d else k for d, k in zip(divs, ks)])
+            else:
+                s, r = st.index.search_segmented(q, kmax, seg)
             s, r = s.cpu().tolist(), r.cpu().tolist()
         for i in live:
             k = items[i][1]
@@ -307,18 +377,19 @@ class GpuRetriever:
         st = self.registry.get(name)
         return st is not None and hasattr(st.index, "search_segmented") and hasattr(st, "segment_ranges")
 
-    def search_store(self, name, question, k, metadata_filter=None):
+    def search_store(self, name, question, k, metadata_filter=None, diversity=None):
         """(store, scores, rows) of one question against one store, or None when the store is
         gone or the filter selects no row of it; batched with concurrent callers of the same
         store (filtered questions of a store share one batch, whatever their filters)."""
         if metadata_filter is not None and self._segmentable(name):
-            item = (question, int(k), metadata_filter)
+            item = (question, int(k), metadata_filter) + ((diversity,) if diversity else ())
             if self.batching:
                 return self._batcher(name, None, shared=True).submit(item)
             return self._run_filtered_batch(name, [item])[0]
+        item = (question, int(k)) + ((diversity,) if diversity else ())
         if self.batching:
-            return self._batcher(name, metadata_filter).submit((question, int(k)))
-        return self._run_batch(name, metadata_filter, [(question, int(k))])[0]
+            return self._batcher(name, metadata_filter).submit(item)
+        return self._run_batch(name, metadata_filter, [item])[0]
 
     # ---- several stores in one launch (rfx.union) ------------------------------------------------
     def _union_view(self, names, stores):
@@ -405,18 +476,23 @@ class GpuRetriever:
             mask = view.row_mask(stores, metadata_filter) if metadata_filter is not None else None
             if metadata_filter is not None and mask is None:
                 return [[] for _ in items]
-            kmax = max(k for _, k in items)
+            diverse = any(len(it) > 2 for it in items)  # (question, k, (lambda, fetch_k))
+            kmax = max(it[1] for it in items)
             with torch.cuda.device(view.device):
-                q = self.embedder(view.dim).embed_texts([t for t, _ in items], view.dtype)
-                s, r = view.index.search(q, kmax, row_mask=mask)
-                s, r = s.cpu().numpy(), r.cpu().numpy()
+                q = self.embedder(view.dim).embed_texts([it[0] for it in items], view.dtype)
+                if diverse:  # one selection over the view's rows: diversified across the stores
+                    s, r = _search_diverse(view.index, q, items, 2, mask)
+                    s, r = s.numpy(), r.numpy()
+                else:
+                    s, r = view.index.search(q, kmax, row_mask=mask)
+                    s, r = s.cpu().numpy(), r.cpu().numpy()
             si, lr = view.locate(r)
             # (the members' locks are held: no compaction renumbers them between the search and here)
             gens = [getattr(st, "generation", None) for st in stores]
             out = []
-            for i, (_, k) in enumerate(items):
+            for i, it in enumerate(items):
                 out.append([(float(s[i, j]), int(si[i, j]), int(lr[i, j]), stores[si[i, j]], gens[si[i, j]])
-                            for j in range(k) if r[i, j] >= 0])
+                            for j in range(it[1]) if r[i, j] >= 0])
             return out
         finally:
             if view is not None:
@@ -424,7 +500,7 @@ class GpuRetriever:
             for st in reversed(locked):
                 st.lock.release()
 
-    def _search_union(self, names, question, k, filt):
+    def _search_union(self, names, question, k, filt, diversity=None):
         if self.batching:
             key = (tuple(names), filters.filter_key(filt), id(self.registry))
             with _STATE_LOCK:
@@ -435,22 +511,29 @@ class GpuRetriever:
                     if len(_BATCHERS) >= 4096:
                         _BATCHERS.clear()
                     _BATCHERS[key] = b
-            return b.submit((question, int(k)))
-        return self._run_union_batch(tuple(names), filt, [(question, int(k))])[0]
+            return b.submit((question, int(k)) + ((diversity,) if diversity else ()))
+        return self._run_union_batch(tuple(names), filt, [(question, int(k)) + ((diversity,) if diversity else ())])[0]
 
-    def search(self, store_names, question, k, metadata_filter=None):
+    def search(self, store_names, question, k, metadata_filter=None, diversity=None):
         """Top-k hits over the union of the named stores, rank order (score desc, store order,
         row asc).  metadata_filter: {key: scalar | [scalars]} over upload metadata (rfx.filters).
-        Several flat stores on one device: one scan of their union (rfx.union)."""
+        Several flat stores on one device: one scan of their union (rfx.union).
+        diversity: None, a lambda in [0, 1], or {"lambda": .., "fetch_k": ..}: the k hits are picked by MMR
+        from the fetch_k best (default min(64, max(4k, 16))), in pick order on the union path (diversified
+        across the stores); on the per-store path each store's answer is diversified on its own and the
+        answers merged by score.  ValueError on a sharded or IVF store."""
         k = int(k)
         if not 1 <= k <= 64:
             raise ValueError(f"top_k={k} out of range [1, 64]")
         filt = filters.check_filter(metadata_filter)
+        div = parse_diversity(diversity, k)
+        self.last_diversity = None
         names = list(dict.fromkeys(store_names or []))
         if self.union and len(names) > 1:
-            res = self._search_union(names, question, k, filt)
+            res = self._search_union(names, question, k, filt, div)
             if res is not None:
                 self.last_path = "union"
+                self.last_diversity = "union" if div else None
                 hits = []
                 for sc, si, row, st, gen in res:
                     info = st.row_info(row, gen)
@@ -465,7 +548,11 @@ class GpuRetriever:
             st = self.registry.get(name)
             if st is None or st.index.rows == 0:
                 continue
-            res = self.search_store(name, question, k, filt)
+            if div and not _diversity_ok(st):
+                raise ValueError(DIVERSITY_ERROR)
+            res = self.search_store(name, question, k, filt, div)
+            if div:
+                self.last_diversity = "store"
             if res is None:
                 continue
             st, s, r = res
