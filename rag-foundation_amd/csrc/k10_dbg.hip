@@ -47,6 +47,19 @@ int launch_scan_screen_dbg(const MfmaPlan& p, int variant, const int8_t* X, cons
     RFX_K10V(10, 2097152 + 8388608 + 8192)
     RFX_K10V(10, 2097152 + 8388608 + 65536)
     RFX_K10V(10, 2097152 + 8388608 + 33554432)  // one wave DMAs the tile records (round 6 A/B)
+    // round 8 (parent = the first line above): 16777216 fast-path selects hoisted, 67108864 running stream state,
+    // 134217728 fragment offsets, 268435456 / 536870912 refresh every 16th / 64th tile from tile 64 on
+    RFX_K10V(10, 2097152 + 8388608 + 32)
+    RFX_K10V(10, 2097152 + 8388608 + 268435456 + 32)
+    RFX_K10V(10, 2097152 + 8388608 + 536870912 + 32)
+    RFX_K10V(10, 2097152 + 8388608 + 67108864)
+    RFX_K10V(10, 2097152 + 8388608 + 134217728)
+    RFX_K10V(10, 2097152 + 8388608 + 67108864 + 134217728 + 16777216)
+    RFX_K10V(10, 2097152 + 8388608 + 268435456)
+    RFX_K10V(10, 2097152 + 8388608 + 67108864 + 268435456)  // running state + thinned refresh, without the two small items
+    RFX_K10V(10, 2097152 + 8388608 + 67108864 + 134217728 + 16777216 + 268435456)
+    RFX_K10V(10, 2097152 + 8388608 + 67108864 + 134217728 + 16777216 + 536870912)
+    RFX_K10V(10, 2097152 + 8388608 + 67108864 + 134217728 + 16777216 + 268435456 + 512)
     case 64:  // the 64-queries-per-wave kernel (k_scan_screen64.h; its plan: RFX_K10_Q64=1, one list per workgroup)
       if (p.lists_per_block != 1) return -1;
       return k10q::launch_768(10, grid, st, X, tm, sts, Qc, qe2, nq, ntiles, tau, cs, cr, dr, p.n_lists, nullptr,

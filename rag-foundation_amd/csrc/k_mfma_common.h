@@ -73,6 +73,15 @@ __device__ __forceinline__ void bdma_nt(v4i32 rsrc, uint32_t voff, uint32_t lds_
                "s"(rsrc), "s"(lds_addr)
                : "memory", "m0");
 }
+// bdma_nt with a wave-uniform byte offset in SGPRs (soffset: added to the memory address only, never to the
+// LDS destination), for a descriptor that stays put while the stream advances.  The M0 write comes first and
+// s_nop 3 follows it: five wait states before the load for a descriptor or offset that the compiler may
+// still have moved through v_readfirstlane, and M0's own one (one instruction fewer than bdma_nt).
+__device__ __forceinline__ void bdma_nt_soff(v4i32 rsrc, uint32_t voff, uint32_t soff, uint32_t lds_addr) {
+  asm volatile("s_mov_b32 m0, %3\n\ts_nop 3\n\tbuffer_load_dwordx4 %0, %1, %2 offen nt lds" ::"v"(voff), "s"(rsrc),
+               "s"(soff), "s"(lds_addr)
+               : "memory", "m0");
+}
 // Same at device scope (sc1: misses this CU's L1, sees other workgroups' atomics).
 __device__ __forceinline__ void bdma_sc1(v4i32 rsrc, uint32_t voff, uint32_t lds_addr) {
   asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen sc1 lds" ::"v"(voff),

@@ -35,6 +35,7 @@
 // Algorithmic bytes per tile: 32 * D (codes) + 16 (the tile's metadata record).
 #pragma once
 #include "k_mfma_common.h"
+#include "k10_stream.h"  // (after the HIP runtime: __host__ __device__)
 
 namespace rfx {
 namespace k10 {
@@ -104,8 +105,18 @@ static_assert(kSlot / 1024 == kWaves * kGPW && kTauGPW == 2, "DMA pieces per wav
 
 // the slot table is re-read at the end of these tiles (used two tiles later); debug MODE 16: at every one
 // of the first 16 tiles (the bound's warm-up), then every 4th
+// Round 8 (kModeThin / kModeThin64): beyond tile kThinFrom only every 16th / 64th tile.  A staler slot bound
+// is still a lower bound of a_k (the answer is the same; only slow-path entries can be added), and the
+// bound barely moves once the warm-up is over, while a refresh costs ~115 VALU, four ds_read_b128 and two
+// DMA pieces per wave.  Every counted wait asks this same predicate which tiles refreshed.
+constexpr int kThinBit = 268435456, kThin64Bit = 536870912;  // (kModeThin, kModeThin64 below)
+constexpr int kThinFrom = 64;
 template <int MODE>
 __device__ __forceinline__ bool tau_refresh_tile(int it) {
+  if constexpr ((MODE & (kThinBit | kThin64Bit)) != 0) {
+    const int m = it < kThinFrom ? 3 : ((MODE & kThin64Bit) != 0 ? 63 : 15);
+    return it < ((MODE & 16) != 0 ? 16 : 2) || (it & m) == m;
+  }
   return it < ((MODE & 16) != 0 ? 16 : 2) || (it & 3) == 3;
 }
 
@@ -479,6 +490,12 @@ constexpr int kModeSortMerge = 16384;  // a wave with >= 8 passes in some lane f
 // round 6 (debug A/B): only wave 0 DMAs each tile's 16-B record (1 KB: 64 lane copies) instead of all 8 waves
 // (the per-tile barrier makes it visible to every wave); the other waves' counted waits drop the records
 constexpr int kModeMetaOne = 33554432;
+// round 8: the instruction stream around each MFMA in the steady state (DESIGN §4.10 "Round 8")
+constexpr int kModeFastSel = 16777216;   // the fast path's odd / even selects hoisted into set_bounds
+constexpr int kModeRunAddr = 67108864;   // the stream's source and ring slot as running state (k10_stream.h)
+constexpr int kModeFragOff = 134217728;  // fragment reads: one lane-constant offset per k-step + the slot's bytes
+constexpr int kModeThin = kThinBit;      // slot-table refresh every 16th tile from tile kThinFrom on
+constexpr int kModeThin64 = kThin64Bit;  // ... every 64th
 template <int KL, int D, bool MASK, int RING = kRing, int MODE = 0, int NW = kWaves>
 __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* __restrict__ X, const uint4* __restrict__ tmeta,
                                                              const uint32_t* __restrict__ stats,
@@ -506,6 +523,7 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
 
   const int tid = threadIdx.x;
   const int w = tid >> 6, lane = tid & 63;
+  const int wu = __builtin_amdgcn_readfirstlane(w);  // the same value in an SGPR (kModeRunAddr's LDS destinations)
   const int half = lane >> 5;
   const int range = blockIdx.x;
   const int qg = blockIdx.y * QG;
@@ -660,6 +678,10 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
   const bool qlive = q < nq;
   float tf_own = qlive ? -__builtin_inff() : __builtin_inff();
   float tf_oth = (odd ? q - 16 : q + 16) < nq ? -__builtin_inff() : __builtin_inff();  // the partner lane's query
+  // kModeFastSel: the bounds in the order of the lane's two maxima (m0: query block 0, m1: block 1), selected
+  // here, where the bounds change, instead of selecting the maxima at every tile
+  constexpr bool FSEL = (MODE & kModeFastSel) != 0 && (MODE & 64) == 0;
+  float tf_m0 = odd ? tf_oth : tf_own, tf_m1 = odd ? tf_own : tf_oth;
   auto set_bounds = [&]() {
     if constexpr ((MODE & 64) != 0) {
       ti_own = ibound(thr);
@@ -673,6 +695,10 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
         tf_oth = __uint_as_float(odd ? r[0] : r[1]);
       } else {
         tf_oth = __shfl_xor(tf_own, 16);
+      }
+      if constexpr (FSEL) {
+        tf_m0 = odd ? tf_oth : tf_own;
+        tf_m1 = odd ? tf_own : tf_oth;
       }
     }
   };
@@ -700,6 +726,25 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
     f.a[1] = *(const uint4*)(p + 16 * kRowB);
     return f;
   };
+
+  // kModeFragOff: the lane's byte offset in a slot for each k-step of a stage (row and swizzled chunk, constant
+  // for the whole scan, behind an empty asm so that it stays in its register) plus the slot's byte position,
+  // a running wave-uniform value: one v_add per k-step, the second row block by the read's offset field
+  constexpr bool FOFF = (MODE & kModeFragOff) != 0;
+  uint32_t foff[KPS];
+#pragma unroll
+  for (int kk = 0; kk < KPS; ++kk) {
+    foff[kk] = (uint32_t)((lane & 15) * kRowB + (((4 * kk + (lane >> 4)) ^ sw) << 4));
+    if constexpr (FOFF) asm volatile("" : "+v"(foff[kk]));
+  }
+  auto read_frag_o = [&](uint32_t slot_off, int kk) -> Frag {
+    const uint8_t* p = lds + (foff[kk] + slot_off);
+    Frag f;
+    f.a[0] = *(const uint4*)p;
+    f.a[1] = *(const uint4*)(p + 16 * kRowB);
+    return f;
+  };
+  uint32_t rd_off = 0u, rd_nxt = RING > 1 ? (uint32_t)kSlot : 0u;  // the slots of stages g and g + 1
 
   // Schedule: stage h's piece goes out at k-step 0 of stage h - (RING - 1) into the slot freed at
   // stage h - RING's barrier; fragments are read one k-step ahead; the stage-end wait + barrier sit
@@ -750,6 +795,27 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
     if (lane == 0) lds_arrive(&ready[0]);  // stage 0's first use of slot 0 counts like every other
   asm volatile("s_barrier" ::: "memory");
 
+  // kModeRunAddr: the loop's pieces from running state.  The prologue above issued stages 0 .. AHEAD - 1 by
+  // the closed form; the cursor stands on the tile of stage AHEAD - 1 and the ring position on the slot of
+  // stage AHEAD.  One descriptor per tile (its base rebased by a 64-bit add, k10_stream.h), the stage's
+  // 256 si bytes in soffset, the wave's LDS destination from SGPRs alone.
+  constexpr bool RUN = (MODE & kModeRunAddr) != 0 && (MODE & 8) == 0;
+  k10s::TileCursor cur = k10s::cursor_at(min((AHEAD - 1) / NST, nt - 1), tb0, tstride, D);
+  v4i32 run_rs = make_rsrc(X + cur.code_byte);
+  uint32_t wr_off = (uint32_t)((AHEAD % RING) * kSlot);
+  const uint32_t wdst0 = lds_base + (uint32_t)(wu * 1024);
+  auto issue_run = [&](const int si) {  // si: the stage's index in its tile (a constant once unrolled)
+    if (si == 0) {
+      k10s::cursor_next_tile(cur, nt, tstride, D);
+      run_rs = make_rsrc(X + cur.code_byte);
+    }
+#pragma unroll
+    for (int u = 0; u < GPW; ++u)
+      bdma_nt_soff(run_rs, laneoff[u], (uint32_t)(si * kSK), wdst0 + wr_off + (uint32_t)(NW * u * 1024));
+    if (si == 0 && (!META1 || w == 0)) bdma(meta_rsrc, cur.rec_byte, lds_base + kMetaOff + cur.mslot * 1024u);
+    wr_off = k10s::ring_next(wr_off, kSlot, RING * kSlot);
+  };
+
   Frag fr[NF];
 #pragma unroll
   for (int p = 0; p < PF; ++p) fr[p] = read_frag(0, p);
@@ -776,7 +842,10 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
       hit = (odd ? m1 : m0) >= ti_own || (odd ? m0 : m1) >= ti_oth;
     } else {
       const float st_t = *(const float*)(lds + kMetaOff + (it % kMR) * 1024 + lane * 16);
-      hit = (float)(odd ? m1 : m0) * st_t >= tf_own || (float)(odd ? m0 : m1) * st_t >= tf_oth;
+      if constexpr (FSEL)  // the same two comparisons
+        hit = (float)m0 * st_t >= tf_m0 || (float)m1 * st_t >= tf_m1;
+      else
+        hit = (float)(odd ? m1 : m0) * st_t >= tf_own || (float)(odd ? m0 : m1) * st_t >= tf_oth;
     }
     if constexpr ((MODE & 512) != 0) hit = hit && nq < 0;  // debug: the slow path compiled in, never taken
     if constexpr ((MODE & 1) == 0) {
@@ -903,7 +972,10 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
             const int h = g + AHEAD;
             if constexpr (DEC)  // the slot's previous stage h - RING read by all 8 waves
               if (h >= RING) lds_spin_ge(&done[h % RING], (uint32_t)(8 * (h / RING)));
-            issue_piece(h, h % RING);
+            if constexpr (RUN)
+              issue_run((s + AHEAD) % NST);
+            else
+              issue_piece(h, h % RING);
           }
         if (kk == KB && TB) {
           if (s == NST - 1) {
@@ -976,16 +1048,19 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
           }
         }
         const int ks = s * KPS + kk;
-        fr[(ks + PF) % NF] = kk + PF < KPS ? read_frag(slot, kk + PF) : read_frag((g + 1) % RING, kk + PF - KPS);
-        const Frag& cur = fr[ks % NF];
+        if constexpr (FOFF)
+          fr[(ks + PF) % NF] = kk + PF < KPS ? read_frag_o(rd_off, kk + PF) : read_frag_o(rd_nxt, kk + PF - KPS);
+        else
+          fr[(ks + PF) % NF] = kk + PF < KPS ? read_frag(slot, kk + PF) : read_frag((g + 1) % RING, kk + PF - KPS);
+        const Frag& cf = fr[ks % NF];
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
 #pragma unroll
         for (int rb = 0; rb < 2; ++rb)
 #pragma unroll
           for (int qb = 0; qb < 2; ++qb)
-            acc4[2 * rb + qb] = ks == 0 ? mfma_i8(cur.a[rb], bq[2 * ks + qb], v4i32{0, 0, 0, 0})
-                                        : mfma_i8(cur.a[rb], bq[2 * ks + qb], acc4[2 * rb + qb]);
+            acc4[2 * rb + qb] = ks == 0 ? mfma_i8(cf.a[rb], bq[2 * ks + qb], v4i32{0, 0, 0, 0})
+                                        : mfma_i8(cf.a[rb], bq[2 * ks + qb], acc4[2 * rb + qb]);
         if constexpr ((MODE & 128) == 0) {
           // where the epilogue of tile it - 1 runs inside tile it (its accumulators stay live until tile
           // it + 1's first k-step): production right after k-step 0 (before stage 0's barrier); debug
@@ -1002,6 +1077,10 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
             }
           }
         }
+      }
+      if constexpr (FOFF) {
+        rd_off = rd_nxt;
+        rd_nxt = k10s::ring_next(rd_nxt, kSlot, RING * kSlot);
       }
     }
 
@@ -1079,14 +1158,17 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
 // Production publishes a list's best only when it rose (kModePubOnChange: the same slot table, fewer
 // atomics): 0.3344 against 0.3461 ms at the shard, 2.039 against 2.038 ms at 10M (profiles/r05/k10_pub_ab_*.txt).
 constexpr int kProdRing = 10;
-constexpr int kProdMode = kModeTileBarrier | kModePubOnChange;
+// Round 8: the lean issue stream (running stream state, fragment offsets, hoisted fast-path selects) and the
+// thinned refresh cadence; the parent schedule stays in the debug library as variant (10, tile barrier + publish on change).
+constexpr int kLeanMode = kModeRunAddr | kModeFragOff | kModeFastSel | kModeThin;
+constexpr int kProdMode = kModeTileBarrier | kModePubOnChange | kLeanMode;
 // The 2-wave kernel (64 queries per workgroup, two workgroups per CU): the per-tile barrier over an 8-slot ring
 // at d 768 (RING >= 2 NST + 2); at d 1024 (NST 4) the per-stage barrier over 8 slots (round 4's schedule), which
 // keeps two workgroups within a CU's LDS
 template <int D>
 constexpr int w2_ring() { return 8; }
 template <int D>
-constexpr int w2_mode() { return D == 768 ? kProdMode : kModePubOnChange; }
+constexpr int w2_mode() { return D == 768 ? kProdMode : (kModePubOnChange | kLeanMode); }
 #define RFX_K10_INSTANTIATE_W2(DV, NAME)                                                                      \
   int NAME(int kl, dim3 grid, hipStream_t st, const int8_t* X, const uint4* tm, const uint32_t* sts,           \
            const int8_t* Qc, const float* qe2, int nq, int ntiles, uint32_t* tau, float* cs, int* cr,          \

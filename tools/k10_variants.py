@@ -2,9 +2,11 @@
 corpus in bursts of back-to-back launches, variants interleaved over rounds (the chip's clock
 settles per workload; cdna_hip_programming.md §5.4 rule 24).
 
-variant = 10**8 * RING + MODE (k10_dbg.hip; round 5 first used 10**7 * RING + MODE, round 4 100000 * RING + MODE, round 3 1000 * RING + MODE): RING in {4, 6, 8, 10, 12}; MODE 1 = no top-k fold,
+--variants RING:MODE,... (the library takes 10**8 * RING + MODE, k10_dbg.hip; round 5 first used 10**7 * RING + MODE, round 4 100000 * RING + MODE, round 3 1000 * RING + MODE): RING in {4, 6, 8, 10, 12}; MODE 1 = no top-k fold,
 8 = no corpus stream after the prologue, 9 = both; 32 = count slow-path entries (reported, not
-timed); 64 = the store-wide integer fast-path bound."""
+timed); 64 = the store-wide integer fast-path bound.  Round 8's bits lie above 10**8 (k_scan_screen.h kModeRunAddr ...), so the
+number alone no longer says where RING ends: write such a variant as RING:MODE (--variants 10:77594624).  --all-rounds prints every round's
+figure (the spread of one variant over the rounds is the noise a difference has to clear)."""
 import argparse
 import ctypes
 import json
@@ -26,8 +28,9 @@ ap.add_argument("--nq", type=int, default=256)
 ap.add_argument("--k", type=int, default=10)
 ap.add_argument("--rounds", type=int, default=4)
 ap.add_argument("--burst", type=int, default=30)
-ap.add_argument("--variants", default="1010485760,800000000,1010485761,1010486272")
+ap.add_argument("--variants", default="10:10485760,8:0,10:10485761,10:10486272")
 ap.add_argument("--seconds", type=float, default=0.0, help="one variant back to back for this long (power sampling)")
+ap.add_argument("--all-rounds", action="store_true", help="print each round's ms per launch as well")
 ap.add_argument("--validate", action="store_true", help="each variant's two-pass answer must equal production's")
 a = ap.parse_args()
 f = _lib.lib.rfx_dbg_screen_variant
@@ -40,7 +43,23 @@ ix.enable_screen(1)
 q = synth_rows(1, 0, a.nq, 768, "bf16")
 ws = torch.empty(ix.workspace_bytes(a.nq, a.k), dtype=torch.uint8, device="cuda")
 st = _lib.stream_ptr()
-variants = [int(v) for v in a.variants.split(",")]
+# A variant is written RING:MODE.  The number 10**8 * RING + MODE that the library takes does not say where RING
+# ends once MODE reaches 10**8 (round 8's bits do), so a bare number is not accepted.
+MODES = {}
+variants = []
+for tok in a.variants.split(","):
+    if ":" not in tok:
+        sys.exit(f"variant {tok}: write it as RING:MODE, e.g. 10:10485760")
+    ring, mode = (int(x) for x in tok.split(":"))
+    if ring not in (4, 6, 8, 10, 12) or mode < 0 or 10**8 * ring + mode >= 2**31:
+        sys.exit(f"variant {tok}: RING must be one of 4, 6, 8, 10, 12 and 10**8 * RING + MODE below 2**31")
+    variants.append(10**8 * ring + mode)
+    MODES[variants[-1]] = mode
+
+
+def mode_of(v):
+    """The MODE bits of a variant number (the low bits are all the tool looks at)."""
+    return MODES[v]
 
 
 def launch(v):
@@ -62,7 +81,7 @@ if a.validate:  # every variant's two-pass answer (no fallback) against the prod
     vs.restype = ctypes.c_int
     ref_s, ref_r = ix.search(q, a.k)
     for v in variants:
-        if (v % 10000000) & (1 | 8 | 512):  # timing-only variants (wrong results by design)
+        if mode_of(v) & (1 | 8 | 512):  # timing-only variants (wrong results by design)
             continue
         s_ = torch.empty_like(ref_s)
         r_ = torch.empty_like(ref_r)
@@ -93,7 +112,7 @@ if a.seconds > 0:  # steady state of ONE variant (rocm-smi samples power / sclk 
 cnt = _lib.lib.rfx_dbg_screen_counts
 cnt.argtypes = [ctypes.c_uint64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64)]
 cnt.restype = ctypes.c_int
-for v in [v for v in variants if (v % 10000000) & 32]:  # slow-path entries of one launch (MODE 32 counter)
+for v in [v for v in variants if mode_of(v) & 32]:  # slow-path entries of one launch (MODE 32 counter)
     launch(v)
     torch.cuda.synchronize()
     n = ctypes.c_uint64()
@@ -101,7 +120,7 @@ for v in [v for v in variants if (v % 10000000) & 32]:  # slow-path entries of o
     ntiles = -(-a.rows // 32)
     print(json.dumps({"variant": v, "slow_path_wave_entries": n.value, "wave_tiles": ntiles * 8,
                       "frac": round(n.value / (ntiles * 8), 5)}))
-variants = [v for v in variants if not (v % 10000000) & 32]
+variants = [v for v in variants if not mode_of(v) & 32]
 res = {v: [] for v in variants}
 for rnd in range(a.rounds):
     for v in (variants if rnd % 2 == 0 else variants[::-1]):
@@ -116,4 +135,8 @@ for rnd in range(a.rounds):
         res[v].append(e0.elapsed_time(e1) / a.burst)
 out = {str(v): {"ms_per_launch_min": round(min(t), 4), "ms_per_launch_med": round(sorted(t)[len(t) // 2], 4)}
        for v, t in res.items()}
+if a.all_rounds:
+    for v, t in res.items():
+        out[str(v)]["rounds"] = [round(x, 4) for x in t]
+        out[str(v)]["spread"] = round(max(t) - min(t), 4)
 print(json.dumps({"rows": a.rows, "nq": a.nq, "burst": a.burst, "rounds": a.rounds, "variants": out}, indent=1))
