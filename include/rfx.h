@@ -300,6 +300,10 @@ int rfx_search_plan(rfx_index_t h, int64_t nq, int k, int* out_kernel);
  * {kept screen candidates, survivors re-scored (-1 = sent to the fallback)} into diag_h [nq][2], and
  * whether the exact fallback ran for the batch (*fallback_h != 0). */
 int rfx_screen_diag(rfx_index_t h, int64_t nq, int k, const void* ws_d, int32_t* diag_h, uint32_t* fallback_h);
+/* After a two-pass search of 1..8 questions (kernel 11) on `stream` (this call synchronises it): whether the
+ * screen could not prove its answer and the exact fallback answered (*fallback_h != 0).  Read-only: the gate
+ * word of the index's search state for that stream, as the last kernel-11 launch on it left it. */
+int rfx_screen_valu_diag(rfx_index_t h, void* stream, uint32_t* fallback_h);
 /* The score rule every rfx_search* answer follows (one rule for every plan, round 5): a score is fl32 of
  * the f64 sum of the exact products of the stored row and query, the order (score desc, row asc).
  * rfx_rescore_topk applies it in place to a [nq][k] answer assembled from the building blocks

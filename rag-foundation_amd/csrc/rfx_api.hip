@@ -2146,6 +2146,20 @@ int rfx_screen_diag(rfx_index_t h, int64_t nq, int k, const void* ws_d, int32_t*
   return RFX_OK;
 }
 
+int rfx_screen_valu_diag(rfx_index_t h, void* stream, uint32_t* fallback_h) {
+  auto ix = get(h);
+  if (!ix || !fallback_h) return fail(RFX_EINVAL, "unknown index handle / null out");
+  RFX_RLOCK(ix);
+  RFX_HIP(hipSetDevice(ix->device));
+  std::unique_lock<std::mutex> slk(ix->state_mu);
+  auto it = ix->fused_state.find((hipStream_t)stream);
+  if (it == ix->fused_state.end()) return fail(RFX_EINVAL, "no one-launch search has run on this stream");
+  RFX_HIP(hipStreamSynchronize((hipStream_t)stream));
+  // the gate word kernel 11's last block wrote (k_screen_valu.hip: state + 24); read only
+  RFX_HIP(hipMemcpy(fallback_h, it->second + rfx::kScreenValuState + 24, 4, hipMemcpyDeviceToHost));
+  return RFX_OK;
+}
+
 // ---- embedding -------------------------------------------------------------------------------------
 int rfx_embed_weights(int V, int dim, uint64_t seed, void* wt_d, void* stream) {
   if (V <= 0 || (V & (V - 1)) || V % 16 != 0) return fail(RFX_EINVAL, "V=%d must be a power of two >= 16", V);

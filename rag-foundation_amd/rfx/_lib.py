@@ -165,6 +165,7 @@ SIGNATURES = {
     "rfx_index_screen_state": ([_u64, _pi, _pi64, _pi], _i),
     "rfx_index_screen_read": ([_u64, _i64, _i64, _p, _p, _p, _p], _i),
     "rfx_screen_diag": ([_u64, _i64, _i, _p, _p, _p], _i),
+    "rfx_screen_valu_diag": ([_u64, _p, _p], _i),
     "rfx_scan_topk_masked": ([_u64, _p, _i64, _i, _p, _i64, _p, _p, _p, _sz, _p], _i),
     "rfx_topk_merge": ([_p, _p, _i, _i64, _i64, _i, _i64, _p, _p, _p], _i),
     "rfx_scan_list_len": ([_u64, _i64, _i, _p], _i),

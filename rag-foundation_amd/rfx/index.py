@@ -352,6 +352,14 @@ class DeviceIndex:
             check(lib.rfx_screen_diag(self.handle, int(nq), int(k), ptr(workspace), diag.ctypes.data, ctypes.byref(fb)))
         return diag, bool(fb.value)
 
+    def screen_valu_diag(self, stream=None) -> bool:
+        """After a two-pass search of 1..8 questions (kernel 11) on `stream`: True when the exact fallback
+        answered (rfx_screen_valu_diag; read-only)."""
+        fb = ctypes.c_uint32()
+        with torch.cuda.device(self.device):
+            check(lib.rfx_screen_valu_diag(self.handle, stream_ptr(stream), ctypes.byref(fb)))
+        return bool(fb.value)
+
     def list_len(self, nq: int, k: int) -> int:
         """Length of the sorted candidate lists rfx_scan_topk writes (merge hint)."""
         n = ctypes.c_int()
