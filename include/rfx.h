@@ -479,6 +479,53 @@ int rfx_rerank_candidates(const void* queries_d, int64_t nq, int dtype, const vo
 int rfx_quantize(const void* rows_d, int64_t n, int dim, int dtype, int8_t* codes_d, float* inv_d,
                  void* stream);
 
+/* ---- lexical index: BM25 over the hashed term features, fused with the dense top-k -------
+ * The keyword half of a hybrid answer.  The retrieval slice of ask_stream (gemini_rag.py:517-551) ranks by one
+ * signal; a question that turns on a part number or an error code wants the literal token.  The handle keeps, on
+ * one device, the CSR rfx_featurize writes for the embedder (per row: one packed u32 per entry, bucket | tf << 16
+ * with tf = |count|, zero counts dropped; len_r = sum of tf, -1 for a dead row) and, on the host, exact int64
+ * statistics over the LIVE rows: N, df_t, sum of len_r.  Tombstoning subtracts a row, so the statistics always
+ * equal those of a fresh index over the live rows.
+ *   score(q, r) = fl32( sum over t in q and r of w_t * (tf * (k1 + 1)) / (tf + B_r) ), in f64,
+ *   w_t = fl32(idf_t * qtf_t), idf_t = log(1 + ((N - df_t) + 0.5) / (df_t + 0.5)),
+ *   B_r = k1 * ((1 - b) + b * (len_r / avgdl)), avgdl = (sum of len_r) / N.
+ * Order: score desc, row asc; a row sharing no bucket with the question, a dead row and a row outside the row
+ * mask never rank; padding (-inf, -1).  V <= 65536; rows < 2^31 - 1. */
+typedef uint64_t rfx_lex_t;
+int rfx_lex_create(int V, int device, rfx_lex_t* out);
+int rfx_lex_destroy(rfx_lex_t h);
+/* Append n rows: a host CSR as rfx_featurize writes it (indptr_h [n + 1]).  Synchronous (pinned staging). */
+int rfx_lex_add(rfx_lex_t h, const int32_t* indptr_h, const int32_t* bucket_h, const int16_t* count_h, int64_t n);
+int rfx_lex_tombstone(rfx_lex_t h, const int64_t* rows_h, int64_t n);
+/* Any output may be NULL.  total_len: over live rows. */
+int rfx_lex_info(rfx_lex_t h, int64_t* rows, int64_t* live, int64_t* nnz, int64_t* total_len);
+/* df_t of every bucket: out [V] (host) */
+int rfx_lex_df(rfx_lex_t h, int64_t* out);
+int rfx_lex_search_workspace_bytes(rfx_lex_t h, int64_t nq, int k, size_t* out_bytes);
+/* nq in 1..1024 questions as a host CSR (may be freed on return), k in 1..64, k1 >= 0, b in [0, 1] (f32, widened).
+ * mask_d (may be NULL): row mask as rfx_search_masked; no row of an all-zero mask word is read.  Outputs [nq][k]
+ * (device).  RFX_EINVAL, with nothing enqueued and the outputs untouched: k, nq, k1 or b out of range, a bucket
+ * >= V, a non-monotone indptr, a mask or workspace that is too small, and a batch whose questions hold more
+ * than nq * min(V, 4096) distinct buckets in all (the room the workspace has for the question entries).
+ * Workspace: the question entries (8 B each), one dense f32 weight table of V entries per question slot
+ * (ceil(nq / 8) * 8 * V * 4 bytes: 16 MB for 1,024 questions at V 4096, 268 MB at V 65,536) and the candidate
+ * lists (nq * 256 * {4, 16, 64} * 8 bytes). */
+int rfx_lex_search(rfx_lex_t h, const int32_t* q_indptr_h, const int32_t* q_bucket_h, const int16_t* q_count_h,
+                   int64_t nq, int k, float k1, float b, const uint32_t* mask_d, int64_t mask_words, float* scores_d,
+                   int64_t* rows_d, void* ws, size_t ws_bytes, void* stream);
+/* Reciprocal-rank fusion, one launch for the batch.  Per question a dense list (dense_rows_d [nq][n_dense_max], its
+ * first n_dense_h[q] entries) and a lexical list (likewise), in the order the searches return them; rows < 0 are
+ * padding; the rank of an entry is 1 + the valid entries before it.  Each distinct row scores, in f64 with every
+ * operation rounded on its own, f = A / (c + rank_d) + (1 - A) / (c + rank_l), A = alpha_h[q], c = rrf_c (a list
+ * the row is absent from contributes 0.0).  Output [nq][k]: the k best by (f desc, row asc) with fl32(f), the row
+ * and, when out_ranks_d is not NULL, [nq][k][2] = {rank_d, rank_l} (0 = absent); padding (-inf, -1, 0, 0).
+ * alpha_h / n_dense_h / n_lex_h: host [nq], NULL = 0.5 / the list maxima.  RFX_EINVAL before anything is enqueued:
+ * k or a list length outside 1..64, k > n_dense_max + n_lex_max, nq outside 1..1024, an alpha outside [0, 1] or
+ * NaN, rrf_c < 1. */
+int rfx_lex_fuse(rfx_lex_t h, const int64_t* dense_rows_d, int n_dense_max, const int64_t* lex_rows_d, int n_lex_max,
+                 int64_t nq, int k, const float* alpha_h, const int32_t* n_dense_h, const int32_t* n_lex_h, int rrf_c,
+                 float* out_scores_d, int64_t* out_rows_d, int32_t* out_ranks_d /* may be NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,15 @@ SIGNATURES = {
     "rfx_embed_workspace_bytes": ([_i64, _i, _psz], _i),
     "rfx_embed": ([_p, _p, _p, _i64, _i, _p, _i, _p, _i, _p, _sz, _p], _i),
     "rfx_synth_rows": ([_u64, _i64, _i64, _i, _i, _p, _p], _i),
+    "rfx_lex_create": ([_i, _i, _pu64], _i),
+    "rfx_lex_destroy": ([_u64], _i),
+    "rfx_lex_add": ([_u64, _p, _p, _p, _i64], _i),
+    "rfx_lex_tombstone": ([_u64, _p, _i64], _i),
+    "rfx_lex_info": ([_u64, _pi64, _pi64, _pi64, _pi64], _i),
+    "rfx_lex_df": ([_u64, _p], _i),
+    "rfx_lex_search_workspace_bytes": ([_u64, _i64, _i, _psz], _i),
+    "rfx_lex_search": ([_u64, _p, _p, _p, _i64, _i, ctypes.c_float, ctypes.c_float, _p, _i64, _p, _p, _p, _sz, _p], _i),
+    "rfx_lex_fuse": ([_u64, _p, _i, _p, _i, _i64, _i, _p, _p, _p, _i, _p, _p, _p, _p], _i),
 }
 
 for _name, (_args, _res) in SIGNATURES.items():

@@ -100,6 +100,10 @@ class LocalGpuRag:
         # lambda of every question; unset = off (the k best chunks as they come)
         lam = os.environ.get("RFX_MMR_LAMBDA", "").strip()
         self.diversity = float(lam) if lam else None
+        # hybrid retrieval (BM25 fused with the dense top-k): RFX_HYBRID_ALPHA is the default
+        # alpha of every question (1 = dense only, 0 = keywords only); unset = off
+        alpha = os.environ.get("RFX_HYBRID_ALPHA", "").strip()
+        self.hybrid = float(alpha) if alpha else None
         self.is_mock = True
 
     # -------- Stores --------
@@ -150,13 +154,22 @@ class LocalGpuRag:
 
     # -------- Query (sync & stream) --------
     def retrieve(self, question: str, store_names: Sequence[str], k: Optional[int] = None,
-                 metadata_filter: Optional[Any] = None, diversity: Optional[Any] = None):
+                 metadata_filter: Optional[Any] = None, diversity: Optional[Any] = None,
+                 hybrid: Optional[Any] = None):
         """Top-k hits.  k: the request's top_k (the reference route drops it,
         chat.py:66), default self.top_k; 1..64.  diversity: a lambda in [0, 1] or {"lambda": ..,
         "fetch_k": ..} picks the k hits by MMR from the fetch_k best (GpuRetriever.search); None = the
-        default of RFX_MMR_LAMBDA (unset: off)."""
+        default of RFX_MMR_LAMBDA (unset: off).  hybrid: an alpha in [0, 1] or {"alpha", "fetch_k", "rrf_c",
+        "k1", "b"} fuses the dense answer with the BM25 answer over the chunk texts (GpuRetriever.search;
+        ValueError on a sharded or IVF store and together with diversity); None = the default of
+        RFX_HYBRID_ALPHA (unset: off)."""
         filt = metadata_filter if self.apply_filters else None
         div = self.diversity if diversity is None else diversity
+        hyb = self.hybrid if hybrid is None else hybrid
+        if hyb is not None:
+            kw = {} if div is None else {"diversity": div}
+            return self.retriever.search(list(store_names or []), question, self.top_k if k is None else int(k),
+                                         metadata_filter=filt, hybrid=hyb, **kw)
         if div is None:
             return self.retriever.search(list(store_names or []), question, self.top_k if k is None else int(k),
                                          metadata_filter=filt)
@@ -164,18 +177,21 @@ class LocalGpuRag:
                                      metadata_filter=filt, diversity=div)
 
     def ask(self, *, contents: Any, store_names: Sequence[str], metadata_filter: Optional[Any], model: str,
-            system: Optional[str] = None, top_k: Optional[int] = None, diversity: Optional[Any] = None) -> Any:
+            system: Optional[str] = None, top_k: Optional[int] = None, diversity: Optional[Any] = None,
+            hybrid: Optional[Any] = None) -> Any:
         with observe("generate"):
-            hits = self.retrieve(contents_to_text(contents), store_names, top_k, metadata_filter, diversity)
+            hits = self.retrieve(contents_to_text(contents), store_names, top_k, metadata_filter, diversity, hybrid)
             return build_response(hits, store_names)
 
     def ask_stream(self, *, contents: Any, store_names: Sequence[str], metadata_filter: Optional[Any], model: str,
-                   system: Optional[str] = None, top_k: Optional[int] = None, diversity: Optional[Any] = None):
+                   system: Optional[str] = None, top_k: Optional[int] = None, diversity: Optional[Any] = None,
+                   hybrid: Optional[Any] = None):
         """The reference's keyword set plus an optional top_k (callers that do not pass it get
         self.top_k, so the reference call site chat.py:499-505 works unchanged)."""
         with observe("generate_stream"):
             text = contents_to_text(contents)
-            resp = build_response(self.retrieve(text, store_names, top_k, metadata_filter, diversity), store_names)
+            resp = build_response(self.retrieve(text, store_names, top_k, metadata_filter, diversity, hybrid),
+                                  store_names)
         yield SimpleNamespace(text=f"[mock-mode] {text or 'response'}", candidates=None,
                               usage_metadata=SimpleNamespace(prompt_token_count=0, candidates_token_count=0))
         yield resp

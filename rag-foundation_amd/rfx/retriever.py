@@ -11,7 +11,7 @@ import torch
 
 from . import filters
 from .batcher import GroupBatcher
-from .embedder import DEFAULT_MAX_TOKENS, DEFAULT_OVERLAP, Embedder
+from .embedder import DEFAULT_MAX_TOKENS, DEFAULT_OVERLAP, Embedder, featurize_texts
 from .store import registry as default_registry
 from . import union as runion
 
@@ -99,6 +99,49 @@ def parse_diversity(diversity, k: int):
     if not k <= fetch_k <= 64:
         raise ValueError(f"diversity fetch_k={fetch_k} must satisfy k={k} <= fetch_k <= 64")
     return float(lam), fetch_k
+
+
+HYBRID_ERROR = "hybrid needs a flat single-device store and no diversity"
+_HYBRID = "\x00hybrid"  # tag of a store's hybrid batchers (no filter_key starts with NUL)
+
+
+def parse_hybrid(hybrid, k: int):
+    """hybrid (None | alpha | {"alpha": .., "fetch_k": .., "rrf_c": .., "k1": .., "b": ..}) -> None or
+    (alpha, fetch_k, rrf_c, k1, b): reciprocal-rank fusion of the dense and the BM25 answer at fetch_k each
+    (DESIGN §4.14).  0 <= alpha <= 1 (1 = dense only), k <= fetch_k <= 64 (default default_fetch_k(k)),
+    rrf_c >= 1 (60), k1 >= 0 (1.2), 0 <= b <= 1 (0.75)."""
+    if hybrid is None:
+        return None
+    if isinstance(hybrid, dict):
+        unknown = set(hybrid) - {"alpha", "fetch_k", "rrf_c", "k1", "b"}
+        if unknown or "alpha" not in hybrid:
+            raise ValueError(f"hybrid takes 'alpha' and optionally 'fetch_k', 'rrf_c', 'k1', 'b', got {sorted(hybrid)}")
+        opts = hybrid
+    else:
+        opts = {"alpha": hybrid}
+
+    def number(name, default, lo, hi):
+        v = opts.get(name, default)
+        if v is None:
+            v = default
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not lo <= float(v) <= hi:  # (a NaN fails)
+            raise ValueError(f"hybrid {name}={v!r} must be a number in [{lo}, {hi}]")
+        return float(v)
+
+    alpha = number("alpha", None, 0.0, 1.0)
+    k1 = number("k1", 1.2, 0.0, 3.0e38)
+    b = number("b", 0.75, 0.0, 1.0)
+    fetch_k, rrf_c = opts.get("fetch_k"), opts.get("rrf_c", 60)
+    for name, v in (("fetch_k", fetch_k), ("rrf_c", rrf_c)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, int)):
+            raise ValueError(f"hybrid {name}={v!r} must be an integer")
+    fetch_k = default_fetch_k(k) if fetch_k is None else int(fetch_k)
+    if not k <= fetch_k <= 64:
+        raise ValueError(f"hybrid fetch_k={fetch_k} must satisfy k={k} <= fetch_k <= 64")
+    rrf_c = 60 if rrf_c is None else int(rrf_c)
+    if not 1 <= rrf_c <= 2 ** 31 - 1:
+        raise ValueError(f"hybrid rrf_c={rrf_c} must be an integer >= 1")
+    return alpha, fetch_k, rrf_c, k1, b
 
 
 def _diversity_ok(st) -> bool:
@@ -202,6 +245,7 @@ class GpuRetriever:
         self.last_path = None  # "union" | "per-store" (tests, diagnostics)
         self.last_filter_path = None  # "segmented" | "masked": how the last filtered batch was searched
         self.last_diversity = None  # "union" | "store" | None: where the last question was diversified
+        self.last_hybrid = None  # "store" | None: the last question fused a dense and a lexical answer per store
 
     @property
     def registry(self):
@@ -288,6 +332,57 @@ class GpuRetriever:
         if metadata_filter is not None:
             self.last_filter_path = "masked"
         return [_answer(st, s, r, gen) for s, r in res]
+
+    def _run_hybrid_batch(self, name, metadata_filter, items):
+        """Batch runner of a store's hybrid questions, items (question, k, (alpha, fetch_k, rrf_c, k1, b)) that
+        share rrf_c, k1 and b (the batcher's key): one embedding, one dense search at the largest fetch_k, one
+        featurisation of the questions, one BM25 search at the same fetch_k, one fusion with each item's own
+        alpha and list lengths; each item takes its first k.  A filter's row mask applies to both searches."""
+        st = self.registry.get(name)
+        if st is None:
+            return [None] * len(items)
+        if not _diversity_ok(st):
+            raise ValueError(HYBRID_ERROR)
+        _, _, rrf_c, k1, b = items[0][2]
+        fetch = max(it[2][1] for it in items)
+        kmax = max(it[1] for it in items)
+
+        def run():
+            mask = st.row_mask(metadata_filter) if metadata_filter is not None else None
+            if metadata_filter is not None and mask is None:
+                return None
+            with torch.cuda.device(st.device), st.lock:  # no append moves either index between the two searches
+                lex = st.lexical()
+                csr = featurize_texts([it[0] for it in items], lex.V, lex.hash_seed)
+                q = self.embedder(st.dim).embed_csr(*csr, dtype=st.dtype)
+                _, rd = st.index.search(q, fetch, row_mask=mask)
+                _, rl = lex.search(csr, fetch, k1=k1, b=b, row_mask=mask)
+                n = [it[2][1] for it in items]
+                s, r = lex.fuse(rd, rl, kmax, [it[2][0] for it in items], n_dense=n, n_lex=n, rrf_c=rrf_c)
+                s, r = s.cpu().tolist(), r.cpu().tolist()
+            return [(s[i][:it[1]], r[i][:it[1]]) for i, it in enumerate(items)]
+
+        res, gen = _numbered(st, run)
+        if res is None:
+            return [None] * len(items)
+        return [_answer(st, s, r, gen) for s, r in res]
+
+    def _hybrid_batcher(self, name, metadata_filter, hyb):
+        # hybrid questions of a store ride batchers of their own: the existing key with a hybrid tag (and the
+        # parameters one launch shares), so no existing batch ever changes shape
+        tag = f"{_HYBRID}:{hyb[2]}:{hyb[3]!r}:{hyb[4]!r}:{filters.filter_key(metadata_filter)}"
+        key = (name, tag, id(self.registry))
+        with _STATE_LOCK:
+            b = _BATCHERS.get(key)
+            if b is None:
+                if self.registry.on_evict.count(_purge_batchers) == 0:
+                    self.registry.on_evict.append(_purge_batchers)
+                b = GroupBatcher(lambda items, n=name, f=metadata_filter: self._run_hybrid_batch(n, f, items),
+                                 max_batch=256)
+                if len(_BATCHERS) >= 4096:
+                    _BATCHERS.clear()
+                _BATCHERS[key] = b
+            return b
 
     def _run_filtered_batch(self, name, items):
         """Batch runner of a store's filtered questions, items (question, k, filter): the items are grouped
@@ -377,10 +472,18 @@ class GpuRetriever:
         st = self.registry.get(name)
         return st is not None and hasattr(st.index, "search_segmented") and hasattr(st, "segment_ranges")
 
-    def search_store(self, name, question, k, metadata_filter=None, diversity=None):
+    def search_store(self, name, question, k, metadata_filter=None, diversity=None, hybrid=None):
         """(store, scores, rows) of one question against one store, or None when the store is
         gone or the filter selects no row of it; batched with concurrent callers of the same
-        store (filtered questions of a store share one batch, whatever their filters)."""
+        store (filtered questions of a store share one batch, whatever their filters).
+        hybrid: parse_hybrid's tuple; the scores are then the fused ones (masked path under a filter)."""
+        if hybrid is not None:
+            if diversity:
+                raise ValueError(HYBRID_ERROR)
+            item = (question, int(k), tuple(hybrid))
+            if self.batching:
+                return self._hybrid_batcher(name, metadata_filter, hybrid).submit(item)
+            return self._run_hybrid_batch(name, metadata_filter, [item])[0]
         if metadata_filter is not None and self._segmentable(name):
             item = (question, int(k), metadata_filter) + ((diversity,) if diversity else ())
             if self.batching:
@@ -514,22 +617,30 @@ class GpuRetriever:
             return b.submit((question, int(k)) + ((diversity,) if diversity else ()))
         return self._run_union_batch(tuple(names), filt, [(question, int(k)) + ((diversity,) if diversity else ())])[0]
 
-    def search(self, store_names, question, k, metadata_filter=None, diversity=None):
+    def search(self, store_names, question, k, metadata_filter=None, diversity=None, hybrid=None):
         """Top-k hits over the union of the named stores, rank order (score desc, store order,
         row asc).  metadata_filter: {key: scalar | [scalars]} over upload metadata (rfx.filters).
         Several flat stores on one device: one scan of their union (rfx.union).
         diversity: None, a lambda in [0, 1], or {"lambda": .., "fetch_k": ..}: the k hits are picked by MMR
         from the fetch_k best (default min(64, max(4k, 16))), in pick order on the union path (diversified
         across the stores); on the per-store path each store's answer is diversified on its own and the
-        answers merged by score.  ValueError on a sharded or IVF store."""
+        answers merged by score.  ValueError on a sharded or IVF store.
+        hybrid: None, an alpha in [0, 1], or {"alpha", "fetch_k", "rrf_c", "k1", "b"} (parse_hybrid): each store
+        answers with the reciprocal-rank fusion of its dense and its BM25 top fetch_k (alpha 1 = dense only),
+        Hit.score is the fused score, and several stores are merged by it (never a union view).  ValueError
+        (HYBRID_ERROR) on a sharded or IVF store and together with diversity."""
         k = int(k)
         if not 1 <= k <= 64:
             raise ValueError(f"top_k={k} out of range [1, 64]")
         filt = filters.check_filter(metadata_filter)
         div = parse_diversity(diversity, k)
+        hyb = parse_hybrid(hybrid, k)
+        if hyb and div:  # an RRF score is not a similarity: the MMR objective would be meaningless
+            raise ValueError(HYBRID_ERROR)
         self.last_diversity = None
+        self.last_hybrid = None
         names = list(dict.fromkeys(store_names or []))
-        if self.union and len(names) > 1:
+        if self.union and len(names) > 1 and not hyb:
             res = self._search_union(names, question, k, filt, div)
             if res is not None:
                 self.last_path = "union"
@@ -550,9 +661,13 @@ class GpuRetriever:
                 continue
             if div and not _diversity_ok(st):
                 raise ValueError(DIVERSITY_ERROR)
-            res = self.search_store(name, question, k, filt, div)
+            if hyb and not _diversity_ok(st):
+                raise ValueError(HYBRID_ERROR)
+            res = self.search_store(name, question, k, filt, div, hyb)
             if div:
                 self.last_diversity = "store"
+            if hyb:
+                self.last_hybrid = "store"
             if res is None:
                 continue
             st, s, r = res

@@ -206,6 +206,10 @@ class LocalStore:
         self._moves = 0
         self._prev = None
         self.on_compact = []  # callbacks(store name) before this object's rows are renumbered
+        # the lexical (BM25) index over the chunk texts (rfx.lexical): derived state, built from
+        # self.rows by every process (RFX_LEXICAL=1: at open; otherwise at the first lexical() call)
+        self._lex = None
+        self._lex_dead = set()  # the deleted files whose rows the lexical index has tombstoned
 
     # ---- files -------------------------------------------------------------------------------
     def _p(self, name):
@@ -306,6 +310,7 @@ class LocalStore:
         self.spec = man.get("index") or {"kind": "flat"}
         self.ivf_meta = None
         self._drop_ivf()
+        self._drop_lex()
         self.rows, self.files = [], {}
         self.meta_bytes = self.files_bytes = self.tombs = 0
         self.version = -1
@@ -345,6 +350,7 @@ class LocalStore:
                 if man["version"] == self.version:
                     self.ivf_meta = man.get("ivf")
                     self._ivf_catch_up()
+                    self._lex_catch_up()
                     self._maybe_screen()
             else:
                 self._reset(man)
@@ -373,6 +379,7 @@ class LocalStore:
         self.version = man["version"]
         self._stat = stat
         self._ivf_catch_up()
+        self._lex_catch_up()
         self._maybe_screen()
 
     def _apply_file_record(self, r):
@@ -427,6 +434,7 @@ class LocalStore:
                 self._rollback(first)
                 raise
             self._ivf_catch_up()
+            self._lex_catch_up()
             self._maybe_screen()
             return file_id, first
 
@@ -551,6 +559,7 @@ class LocalStore:
                     self.index.rows_sync(self._p("rows.rfx"), len(rows))
             self._prev = prev
             self._drop_ivf()  # the lists hold old row ids; the centroids (ivf_meta, ivf-*.bin) do not
+            self._drop_lex()  # old row ids too: rebuilt from the renumbered rows (the same scores: live-row statistics)
         finally:
             self._moves += 1
 
@@ -599,6 +608,7 @@ class LocalStore:
             raise
         self._gc_generations()  # the old generation's data files
         self._ivf_catch_up()
+        self._lex_catch_up()
         self._maybe_screen()
         return {"rows_before": before, "rows": kept}
 
@@ -705,6 +715,43 @@ class LocalStore:
             self.ivf, self.ivf_id = ivf, cid
         self.ivf.add_from(self.index, self.index.rows)
 
+    # ---- lexical index ------------------------------------------------------------------
+    def _drop_lex(self):
+        if self._lex is not None:
+            self._lex.close()
+        self._lex = None
+        self._lex_dead = set()
+
+    def _lex_catch_up(self, build=False):
+        """Bring this process's lexical index up to the committed rows and deletions (caller holds self.lock):
+        the rows appended since (the host featurises their chunk texts) and the rows of the files deleted
+        since.  Without an index it does nothing, unless `build` (lexical()) or RFX_LEXICAL=1 ask for one."""
+        if self._lex is None:
+            if not (build or os.environ.get("RFX_LEXICAL", "0") == "1"):
+                return
+            from .lexical import LexIndex
+            self._lex = LexIndex(device=self.device)
+        lex = self._lex
+        n = lex.rows
+        if n > len(self.rows):  # (cannot happen: a reload or a compaction drops the index)
+            self._drop_lex()
+            return self._lex_catch_up(build=True)
+        for lo in range(n, len(self.rows), 8192):
+            lex.add_texts([t for _, t in self.rows[lo:lo + 8192]])
+        for fid, f in self.files.items():
+            if f["deleted"] and fid not in self._lex_dead:
+                if f["n"]:
+                    lex.tombstone(np.arange(f["first"], f["first"] + f["n"], dtype=np.int64))
+                self._lex_dead.add(fid)
+
+    def lexical(self):
+        """The store's lexical index (rfx.lexical.LexIndex), caught up with the committed rows: row r of it is
+        row r of the store.  Built on the first call (or at open with RFX_LEXICAL=1); callers search it under
+        self.lock, so no append moves it meanwhile."""
+        with self.lock:
+            self._lex_catch_up(build=True)
+            return self._lex
+
     def _maybe_screen(self):
         """Large stores (d 768 / 1024) answer with the exact two-pass scan: an int8
         copy of the rows (dim bytes per row, kept current by every append / tombstone inside librfx)
@@ -769,6 +816,7 @@ class LocalStore:
             except BaseException:
                 self._rollback(None)
                 raise
+            self._lex_catch_up()
             self._auto_compact()
             return True
 
@@ -895,6 +943,7 @@ class LocalStore:
     def close(self):
         with self.lock:
             self._drop_ivf()
+            self._drop_lex()
             if self.index is not None:
                 self.index.close()
 
