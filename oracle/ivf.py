@@ -13,6 +13,9 @@ below say which kernel implements each step.  Every step is integer arithmetic o
   quantize (rows and queries; k_ivf.hip quantize_kernel)
     amax = max_d |x_d| (f32);  s = 127 / amax;  q_d = clamp(rint(x_d * s), -127, 127) (int8)
     inv = amax / 127   (amax == 0: q = 0, inv = 0)
+    sub-scale rule: a row whose s is not finite (0 < amax < 127 / FLT_MAX, about 3.7e-37: every denormal
+    amax and the normal ones below 2^-121) is a zero row, q = 0 and inv = 0 — its zero elements would
+    otherwise be 0 * inf = NaN, whose int8 cast is platform-defined
   centroid factor (centroid_finalize_kernel)
     f_c = 1 / sqrt(f32(sum_d qc_d^2))                        (0 for an all-zero centroid)
   coarse score of int8 vector x against centroid c (exact int dot, < 2^24 so exact in f32)
@@ -41,9 +44,13 @@ def quantize(x: np.ndarray):
     amax = amax.astype(np.float32)
     nz = amax > 0
     s = np.zeros_like(amax)
-    s[nz] = _F(127) / amax[nz]
+    with np.errstate(over="ignore"):
+        s[nz] = _F(127) / amax[nz]
+    sub = np.isinf(s)  # the sub-scale rule: a zero row
+    s[sub] = 0
     q = np.rint(x * s[:, None]).clip(-127, 127).astype(np.int8)
     inv = (amax / _F(127)).astype(np.float32)
+    inv[sub] = 0
     return q, inv
 
 

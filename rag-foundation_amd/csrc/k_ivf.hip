@@ -85,12 +85,16 @@ __global__ __launch_bounds__(256) void quantize_kernel(const void* __restrict__ 
     for (int c = lane; c < dim; c += 64) amax = fmaxf(amax, fabsf(load_elem<DT>(X, i * dim + c)));
 #pragma unroll
     for (int off = 32; off; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off));
-    const float s = amax > 0.f ? __fdiv_rn(127.f, amax) : 0.f;
+    // sub-scale rule (oracle/ivf.py): 127 / amax = inf (amax < 127 / FLT_MAX) makes a zero row, codes 0 and
+    // inv 0 — the row's zero elements would be 0 * inf = NaN, clamped to -127
+    const float s0 = amax > 0.f ? __fdiv_rn(127.f, amax) : 0.f;
+    const bool sub = s0 == __builtin_inff();
+    const float s = sub ? 0.f : s0;
     for (int c = lane; c < dim; c += 64) {
       const float q = rintf(__fmul_rn(load_elem<DT>(X, i * dim + c), s));
       codes[i * dim + c] = (int8_t)fminf(fmaxf(q, -127.f), 127.f);
     }
-    if (lane == 0) inv[i] = __fdiv_rn(amax, 127.f);
+    if (lane == 0) inv[i] = sub ? 0.f : __fdiv_rn(amax, 127.f);
   }
 }
 
@@ -566,7 +570,9 @@ __device__ __forceinline__ void seed_lists(float (&ka)[QB][NCH], int (&kg)[NCH],
     int nvalid = 0;
 #pragma unroll
     for (int c = 0; c < NCH; ++c) {
-      key[c] = ka[qi][c] == ka[qi][c] ? ord_f32(ka[qi][c]) : 0u;
+      // (+ 0.0f: -0.0 takes +0.0's key — a fine score is ±0.0 by its dot's sign once inv_r inv_q underflows, and
+      // the rule compares scores as floats: equal, the row id decides.  The list keeps the score's own bits.)
+      key[c] = ka[qi][c] == ka[qi][c] ? ord_f32(ka[qi][c] + 0.0f) : 0u;
       nvalid += (int)__popcll(__ballot(key[c] != 0u));
     }
     uint32_t v = 0u;
@@ -776,7 +782,9 @@ int launch_list_scan(int K, int D, int m, int splits, const int8_t* codes, const
 // c = tid + 256 i).  v = the nprobe-th largest orderable score by a bitwise search on block-wide ballot
 // counts; ties at v are taken by the smallest list ids (a second bitwise search over the tied ids): the
 // set the merge kernel's (score desc, id asc) top-nprobe returns.  The probes are written in no particular
-// order (the pairs are grouped by list next, and every later step is order-free).
+// order (the pairs are grouped by list next, and every later step is order-free).  A coarse score is never -0.0
+// (f32(dot) * f_c: f_c is 0 only for an all-zero centroid, whose dot is 0, and otherwise >= 1 / (127 * 32), far
+// from underflow), so ord_f32's order is the float order here, unlike in seed_lists.
 constexpr int kProbeMaxLists = 4096;
 __global__ __launch_bounds__(256) void probe_select_kernel(const float* __restrict__ S, int m, int nprobe,
                                                            float* __restrict__ ps, int64_t* __restrict__ pid) {
