@@ -464,6 +464,24 @@ int rfx_ivf_search_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, int dt
                           int nprobe, int rerank_k, const void* rows_d, int rows_dtype,
                           float* out_scores_d, int64_t* out_rows_d, void* ws_d, size_t ws_bytes,
                           void* stream);
+/* Metadata-filtered IVF search.  Replaces, for an RFX_INDEX=ivf store, the metadata_filter
+ * that ask_stream accepts and forwards to Gemini's file-search tool (gemini_rag.py:463-469,517-551,
+ * validated and allow-listed at chat.py:295-335) — the case rfx_search_masked serves by reading every row.
+ * row_mask_d / mask_words: the row bitmap of rfx_search_masked (bit r & 31 of word r >> 5 set = row r, an
+ * insertion-order row id, may be returned; one mask for all nq queries; set bits past the last row are
+ * ignored).  row_mask_d == NULL: the unmasked call.  mask_words < (rows + 31) / 32: RFX_EINVAL.
+ * The probes are the unmasked search's (the filter does not change which lists are read).  Result: the
+ * top k by (score desc, row asc) over the rows of the probed lists whose bit is set, padded (-inf, -1) —
+ * the filter applies BEFORE the ranking, never to a finished top-k.  Workspaces: the unmasked calls' sizes
+ * (rfx_ivf_search_workspace_bytes / rfx_ivf_rerank_workspace_bytes).  The re-rank form masks its candidate
+ * search; the re-rank itself needs no mask (its candidates are eligible rows). */
+int rfx_ivf_search_masked(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe,
+                          const uint32_t* row_mask_d, int64_t mask_words, float* out_scores_d,
+                          int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream);
+int rfx_ivf_search_rerank_masked(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k,
+                                 int nprobe, int rerank_k, const void* rows_d, int rows_dtype,
+                                 const uint32_t* row_mask_d, int64_t mask_words, float* out_scores_d,
+                                 int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream);
 /* The re-rank step alone, for a store row-sharded over several devices (rfx/sharded.py
  * ShardedIvf; gemini_rag.py:463-469's file-search tool over an RFX_INDEX=ivf store): cand_d
  * [nq][n_cand] holds GLOBAL row ids (< 0 = padding); the candidates in [row_lo, row_lo + n_rows)

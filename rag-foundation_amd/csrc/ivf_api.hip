@@ -402,8 +402,10 @@ int rfx_ivf_search_workspace_bytes(rfx_ivf_t h, int64_t nq, int k, int nprobe, s
   return RFX_OK;
 }
 
-int rfx_ivf_search(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe, float* out_scores_d,
-                   int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream) {
+// The one body of rfx_ivf_search and rfx_ivf_search_masked (row_mask_d == nullptr: unmasked).
+static int ivf_search(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe,
+                      const uint32_t* row_mask_d, int64_t mask_words, float* out_scores_d, int64_t* out_rows_d, void* ws_d,
+                      size_t ws_bytes, void* stream) {
   auto iv = get(h);
   if (!iv) return api_fail(RFX_EINVAL, "unknown IVF handle");
   if (!valid_dtype(dtype)) return api_fail(RFX_EINVAL, "bad query dtype");
@@ -415,6 +417,10 @@ int rfx_ivf_search(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, in
   if (!ws_d || ws_bytes < L.total) return api_fail(RFX_EINVAL, "workspace too small (%zu < %zu)", ws_bytes, L.total);
   std::lock_guard<std::mutex> lk(iv->mu);
   if (!iv->trained) return api_fail(RFX_EINVAL, "IVF index not trained");
+  // every row id the scan looks up is below iv->rows, so this is the bound of the mask reads
+  if (row_mask_d && mask_words < (iv->rows + 31) / 32)
+    return api_fail(RFX_EINVAL, "row mask has %lld words, the index needs %lld", (long long)mask_words,
+                    (long long)((iv->rows + 31) / 32));
   IVF_HIP(hipSetDevice(iv->device));
   hipStream_t st = (hipStream_t)stream;
   if ((rc = build(*iv, st))) return rc;
@@ -438,7 +444,7 @@ int rfx_ivf_search(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, in
   if (rfx::ivf::launch_group_pairs(pid, (int)(nq * nprobe), iv->nlist, poff, pairs, st))
     return api_fail(RFX_EUNSUPPORTED, "pair grouping rejected");
   if (rfx::ivf::launch_list_scan(L.K, iv->dim, iv->nlist, L.splits, iv->lcodes, iv->linv, iv->lids, iv->off, poff, pairs, nprobe,
-                                 qq, qinv, cs, cr, st))
+                                 qq, qinv, cs, cr, row_mask_d, st))
     return api_fail(RFX_EUNSUPPORTED, "list scan launch rejected (k=%d dim=%d)", k, iv->dim);
   // (the wave lists are sorted best first, empty slots last: the merge reads each only as far as it can
   // still admit)
@@ -447,6 +453,20 @@ int rfx_ivf_search(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, in
     return api_fail(RFX_EUNSUPPORTED, "merge k=%d unsupported", k);
   IVF_HIP(hipGetLastError());
   return RFX_OK;
+}
+
+int rfx_ivf_search(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe, float* out_scores_d,
+                   int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream) {
+  return ivf_search(h, queries_d, nq, dtype, k, nprobe, nullptr, 0, out_scores_d, out_rows_d, ws_d, ws_bytes, stream);
+}
+
+// Metadata-filtered IVF search (include/rfx.h): the probes of the unmasked search, the list scan
+// dropping the rows whose mask bit is clear before they reach a top-k list.
+int rfx_ivf_search_masked(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe,
+                          const uint32_t* row_mask_d, int64_t mask_words, float* out_scores_d, int64_t* out_rows_d,
+                          void* ws_d, size_t ws_bytes, void* stream) {
+  return ivf_search(h, queries_d, nq, dtype, k, nprobe, row_mask_d, mask_words, out_scores_d, out_rows_d, ws_d, ws_bytes,
+                    stream);
 }
 
 // Search with exact re-rank: the IVF search keeps rerank_k (>= k) candidates per query by int8
@@ -463,9 +483,11 @@ int rfx_ivf_rerank_workspace_bytes(rfx_ivf_t h, int64_t nq, int k, int nprobe, i
   return RFX_OK;
 }
 
-int rfx_ivf_search_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe, int rerank_k,
-                          const void* rows_d, int rows_dtype, float* out_scores_d, int64_t* out_rows_d, void* ws_d,
-                          size_t ws_bytes, void* stream) {
+// The one body of rfx_ivf_search_rerank and rfx_ivf_search_rerank_masked: the mask goes to the candidate search
+// only (the re-rank's candidates are eligible rows already).
+static int ivf_search_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe, int rerank_k,
+                             const void* rows_d, int rows_dtype, const uint32_t* row_mask_d, int64_t mask_words,
+                             float* out_scores_d, int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream) {
   auto iv = get(h);
   if (!iv) return api_fail(RFX_EINVAL, "unknown IVF handle");
   if (!valid_dtype(rows_dtype) || !valid_dtype(dtype)) return api_fail(RFX_EINVAL, "bad dtype");
@@ -481,7 +503,8 @@ int rfx_ivf_search_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, int dt
   int64_t* cr = (int64_t*)(ws + al256(ivf) + al256((size_t)nq * rerank_k * 8));
   float* rs = (float*)(ws + al256(ivf) + 2 * al256((size_t)nq * rerank_k * 8));
   int64_t* rr = cr;  // the re-rank kernel rewrites rows in place (padding -> empty sentinel)
-  if ((rc = rfx_ivf_search(h, queries_d, nq, dtype, rerank_k, nprobe, cs, cr, ws, al256(ivf), stream))) return rc;
+  if ((rc = ivf_search(h, queries_d, nq, dtype, rerank_k, nprobe, row_mask_d, mask_words, cs, cr, ws, al256(ivf), stream)))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   IVF_HIP(hipSetDevice(iv->device));
   if (rfx::ivf::launch_rerank(queries_d, dtype, rows_d, rows_dtype, iv->dim, cr, nq, rerank_k, rs, rr, st))
@@ -490,6 +513,21 @@ int rfx_ivf_search_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, int dt
     return api_fail(RFX_EUNSUPPORTED, "merge k=%d unsupported", k);
   IVF_HIP(hipGetLastError());
   return RFX_OK;
+}
+
+int rfx_ivf_search_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe, int rerank_k,
+                          const void* rows_d, int rows_dtype, float* out_scores_d, int64_t* out_rows_d, void* ws_d,
+                          size_t ws_bytes, void* stream) {
+  return ivf_search_rerank(h, queries_d, nq, dtype, k, nprobe, rerank_k, rows_d, rows_dtype, nullptr, 0, out_scores_d,
+                           out_rows_d, ws_d, ws_bytes, stream);
+}
+
+int rfx_ivf_search_rerank_masked(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe,
+                                 int rerank_k, const void* rows_d, int rows_dtype, const uint32_t* row_mask_d,
+                                 int64_t mask_words, float* out_scores_d, int64_t* out_rows_d, void* ws_d,
+                                 size_t ws_bytes, void* stream) {
+  return ivf_search_rerank(h, queries_d, nq, dtype, k, nprobe, rerank_k, rows_d, rows_dtype, row_mask_d, mask_words,
+                           out_scores_d, out_rows_d, ws_d, ws_bytes, stream);
 }
 
 // The re-rank step alone over one shard's rows (rfx/sharded.py ShardedIvf): candidates are global

@@ -644,13 +644,20 @@ __device__ __forceinline__ void seed_lists(float (&ka)[QB][NCH], int (&kg)[NCH],
   }
 }
 
-template <int K, int NC>
+// MASKED: row_mask is the store's row bitmap (bit r & 31 of word r >> 5 over insertion-order row
+// ids, as rfx_search_masked reads it).  A row whose bit is clear is treated exactly like a row past the end of
+// its list: NaN among the seed chunks (seed_lists gives it key 0), offered with valid = false after them, so it
+// never takes a list slot and the K kept are the K best ELIGIBLE rows.  The lookup is one 4-byte vector load at
+// the gid the lane holds anyway; gid < rows <= 32 * mask words (checked by the caller), and a past-the-end
+// lane reads its list's first row (cr = r0), so set bits past the last row are never consulted.  MASKED = false
+// compiles to the code it was before the parameter existed (row_mask is then never read).
+template <int K, int NC, bool MASKED>
 __global__ __launch_bounds__(256) void list_scan_kernel(const int8_t* __restrict__ codes, const float* __restrict__ inv,
                                                         const int* __restrict__ ids, const int64_t* __restrict__ off,
                                                         const int* __restrict__ pair_off, const int* __restrict__ pairs,
                                                         int nprobe, const int8_t* __restrict__ qq,
                                                         const float* __restrict__ qinv, float* __restrict__ cand_s,
-                                                        int* __restrict__ cand_r) {
+                                                        int* __restrict__ cand_r, const uint32_t* __restrict__ row_mask) {
   constexpr int D = NC * 256, NCH = D / 16;  // 16-B chunks per row
   // Round 6: one lane per row.  The codes are in 64-row blocks, chunk-major (gather_rows_kernel), so a wave's
   // load of chunk c of its 64 rows is one 1-KB run; the batch's queries are wave-uniform and come through
@@ -728,20 +735,22 @@ __global__ __launch_bounds__(256) void list_scan_kernel(const int8_t* __restrict
       for (int qi = 0; qi < kQB; ++qi) cand[qi] = (float)acc[qi];
       const float ir = inv[cr];
       const int gid = ids[cr];
+      bool ok = valid;  // the row may take a list slot
+      if constexpr (MASKED) ok = valid && ((row_mask[(uint32_t)gid >> 5] >> (gid & 31)) & 1u);
       if (nch < kSeedChunks) {
 #pragma unroll
         for (int c = 0; c < kSeedChunks; ++c)
           if (c == nch) {
 #pragma unroll
             for (int qi = 0; qi < kQB; ++qi)
-              ka[qi][c] = valid && qi < nb ? __fmul_rn(cand[qi], __fmul_rn(ir, qf[qi])) : __builtin_nanf("");
+              ka[qi][c] = ok && qi < nb ? __fmul_rn(cand[qi], __fmul_rn(ir, qf[qi])) : __builtin_nanf("");
             kg[c] = gid;
           }
         if (++nch == kSeedChunks) seed_lists<K, kQB, kSeedChunks>(ka, kg, lst, w);
       } else {
 #pragma unroll
         for (int qi = 0; qi < kQB; ++qi)
-          if (qi < nb) lst[qi].offer(__fmul_rn(cand[qi], __fmul_rn(ir, qf[qi])), gid, valid);
+          if (qi < nb) lst[qi].offer(__fmul_rn(cand[qi], __fmul_rn(ir, qf[qi])), gid, ok);
       }
     }
     if (nch < kSeedChunks) seed_lists<K, kQB, kSeedChunks>(ka, kg, lst, w);  // (fewer chunks than kept)
@@ -763,11 +772,15 @@ int list_k(int k) { return k <= 4 ? 4 : (k <= 16 ? 16 : (k <= 64 ? 64 : -1)); }
 
 int launch_list_scan(int K, int D, int m, int splits, const int8_t* codes, const float* inv, const int* ids, const int64_t* off,
                      const int* pair_off, const int* pairs, int nprobe, const int8_t* qq, const float* qinv,
-                     float* cs, int* cr, hipStream_t st) {
+                     float* cs, int* cr, const uint32_t* row_mask, hipStream_t st) {
 #define RFX_LS(KV, NCV)                                                                                     \
   if (K == KV && D == NCV * 256) {                                                                          \
-    hipLaunchKernelGGL((list_scan_kernel<KV, NCV>), dim3(m, splits), dim3(256), 0, st, codes, inv, ids, off,  \
-                       pair_off, pairs, nprobe, qq, qinv, cs, cr);                                          \
+    if (row_mask)                                                                                           \
+      hipLaunchKernelGGL((list_scan_kernel<KV, NCV, true>), dim3(m, splits), dim3(256), 0, st, codes, inv, ids, off, \
+                         pair_off, pairs, nprobe, qq, qinv, cs, cr, row_mask);                              \
+    else                                                                                                    \
+      hipLaunchKernelGGL((list_scan_kernel<KV, NCV, false>), dim3(m, splits), dim3(256), 0, st, codes, inv, ids, off, \
+                         pair_off, pairs, nprobe, qq, qinv, cs, cr, nullptr);                               \
     return 0;                                                                                               \
   }
   RFX_LS(4, 1) RFX_LS(4, 2) RFX_LS(4, 3) RFX_LS(4, 4)

@@ -213,7 +213,7 @@ int launch_probe_select(const float* S, int64_t nq, int m, int nprobe, float* ps
 int launch_group_pairs(const int64_t* probes, int P, int m, int* pair_off, int* pairs, hipStream_t st);
 int launch_list_scan(int K, int D, int m, int splits, const int8_t* codes, const float* inv, const int* ids, const int64_t* off,
                      const int* pair_off, const int* pairs, int nprobe, const int8_t* qq, const float* qinv,
-                     float* cs, int* cr, hipStream_t st);
+                     float* cs, int* cr, const uint32_t* row_mask /* nullptr: every row eligible */, hipStream_t st);
 int launch_rerank(const void* Q, int dtq, const void* X, int dtx, int D, const int64_t* cand, int64_t nq, int kc,
                   float* out_s, int64_t* out_r, hipStream_t st, int64_t row_lo = 0, int64_t n_rows = INT64_MAX);
 }  // namespace ivf

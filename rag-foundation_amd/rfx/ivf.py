@@ -130,9 +130,25 @@ class IvfIndex:
         check(lib.rfx_ivf_search_workspace_bytes(self.handle, int(nq), int(k), int(nprobe), ctypes.byref(b)))
         return b.value
 
-    def search(self, queries: torch.Tensor, k: int, nprobe: int, workspace: torch.Tensor = None, stream=None):
-        """Top-k rows per query over the nprobe nearest lists: (scores f32 [nq][k], rows i64 [nq][k])."""
+    def _mask(self, row_mask):
+        """row_mask: None, or the store's device row bitmap (int32 / uint32 words, bit r & 31 of word r >> 5 =
+        row r may be returned; DeviceIndex.mask_tensor) -> (pointer, words).  The C ABI checks its length
+        against the index's rows (RFX_EINVAL when short)."""
+        if row_mask is None:
+            return None, 0
+        if row_mask.dtype not in (torch.int32, torch.uint32) or row_mask.dim() != 1 or not row_mask.is_contiguous():
+            raise ValueError("row mask must be a contiguous 1-D int32/uint32 tensor")
+        if row_mask.device != self._dev():
+            raise ValueError(f"row mask on {row_mask.device}, index on {self._dev()}")
+        return ptr(row_mask), row_mask.numel()
+
+    def search(self, queries: torch.Tensor, k: int, nprobe: int, workspace: torch.Tensor = None, stream=None,
+               row_mask: torch.Tensor = None):
+        """Top-k rows per query over the nprobe nearest lists: (scores f32 [nq][k], rows i64 [nq][k]).
+        row_mask (optional): only rows whose bit is set rank (rfx_ivf_search_masked: the same probes, the
+        filter applied inside the list scan, before any top-k)."""
         q, dt = self._rows(queries)
+        m, mw = self._mask(row_mask)
         nq = q.shape[0]
         out_s = torch.empty((nq, k), dtype=torch.float32, device=self._dev())
         out_r = torch.empty((nq, k), dtype=torch.int64, device=self._dev())
@@ -140,15 +156,20 @@ class IvfIndex:
         ws = workspace if workspace is not None and workspace.numel() >= need else \
             torch.empty(max(need, 1), dtype=torch.uint8, device=self._dev())
         with torch.cuda.device(self.device):
-            check(lib.rfx_ivf_search(self.handle, ptr(q), nq, dt, int(k), int(nprobe), ptr(out_s), ptr(out_r),
-                                     ptr(ws), ws.numel(), stream_ptr(stream)))
+            if m is None:
+                check(lib.rfx_ivf_search(self.handle, ptr(q), nq, dt, int(k), int(nprobe), ptr(out_s), ptr(out_r),
+                                         ptr(ws), ws.numel(), stream_ptr(stream)))
+            else:
+                check(lib.rfx_ivf_search_masked(self.handle, ptr(q), nq, dt, int(k), int(nprobe), m, mw, ptr(out_s),
+                                                ptr(out_r), ptr(ws), ws.numel(), stream_ptr(stream)))
         return out_s, out_r
 
     def search_rerank(self, queries: torch.Tensor, k: int, nprobe: int, rows: torch.Tensor, rerank_k: int = None,
-                      stream=None):
+                      stream=None, row_mask: torch.Tensor = None):
         """IVF search keeping rerank_k candidates (default max(k, 16): lists of up to 16 keep the
         fast scan template), re-scored in f32 against the original rows [rows][dim] (insertion
-        order, e.g. DeviceIndex.read / the brute-force store)."""
+        order, e.g. DeviceIndex.read / the brute-force store).  row_mask: as search (the candidates
+        are then eligible rows only)."""
         q, dt = self._rows(queries)
         if rows.dim() != 2 or rows.shape[1] != self.dim or rows.device != self._dev() or not rows.is_contiguous():
             raise ValueError(f"rows must be a contiguous [n][{self.dim}] tensor on {self._dev()}")
@@ -157,9 +178,10 @@ class IvfIndex:
         rdt = {v: k_ for k_, v in _lib.TORCH_DTYPES.items()}.get(rows.dtype)
         if rdt is None:
             raise ValueError("rows must be float32, bfloat16 or float16")
-        return self._rerank(q, dt, k, nprobe, ptr(rows), _lib.DTYPE_CODES[rdt], rerank_k, stream)
+        return self._rerank(q, dt, k, nprobe, ptr(rows), _lib.DTYPE_CODES[rdt], rerank_k, stream, row_mask)
 
-    def _rerank(self, q, dt, k, nprobe, rows_p, rows_code, rerank_k, stream):
+    def _rerank(self, q, dt, k, nprobe, rows_p, rows_code, rerank_k, stream, row_mask=None):
+        m, mw = self._mask(row_mask)
         rk = max(int(k), 16) if rerank_k is None else int(rerank_k)
         nq = q.shape[0]
         out_s = torch.empty((nq, k), dtype=torch.float32, device=self._dev())
@@ -168,22 +190,29 @@ class IvfIndex:
         check(lib.rfx_ivf_rerank_workspace_bytes(self.handle, nq, int(k), int(nprobe), rk, ctypes.byref(b)))
         ws = torch.empty(max(b.value, 1), dtype=torch.uint8, device=self._dev())
         with torch.cuda.device(self.device):
-            check(lib.rfx_ivf_search_rerank(self.handle, ptr(q), nq, dt, int(k), int(nprobe), rk, rows_p, rows_code,
-                                            ptr(out_s), ptr(out_r), ptr(ws), ws.numel(), stream_ptr(stream)))
+            if m is None:
+                check(lib.rfx_ivf_search_rerank(self.handle, ptr(q), nq, dt, int(k), int(nprobe), rk, rows_p, rows_code,
+                                                ptr(out_s), ptr(out_r), ptr(ws), ws.numel(), stream_ptr(stream)))
+            else:
+                check(lib.rfx_ivf_search_rerank_masked(self.handle, ptr(q), nq, dt, int(k), int(nprobe), rk, rows_p,
+                                                       rows_code, m, mw, ptr(out_s), ptr(out_r), ptr(ws), ws.numel(),
+                                                       stream_ptr(stream)))
         return out_s, out_r
 
     # ---- serving from a store's DeviceIndex (rfx.store, config 5) ------------------------------------
-    def search_index(self, queries: torch.Tensor, k: int, nprobe: int, index, rerank_k: int = None, stream=None):
+    def search_index(self, queries: torch.Tensor, k: int, nprobe: int, index, rerank_k: int = None, stream=None,
+                     row_mask: torch.Tensor = None):
         """search_rerank against a DeviceIndex holding the same rows in the same order (row i of
         this index = row i of `index`).  Tombstoned rows are NaN there, so the exact re-rank drops
-        them.  The caller holds the index owner's lock until the results are read (data_ptr)."""
+        them.  The caller holds the index owner's lock until the results are read (data_ptr).
+        row_mask: the index's own row mask (DeviceIndex.mask_tensor), as search."""
         q, dt = self._rows(queries)
         if index.dim != self.dim or index.device != self.device:
             raise ValueError("index dim / device differ from the IVF index")
         if index.rows < self.rows:
             raise ValueError(f"index holds {index.rows} rows, the IVF lists {self.rows}")
         return self._rerank(q, dt, k, nprobe, ctypes.c_void_p(index.data_ptr()), _lib.DTYPE_CODES[index.dtype],
-                            rerank_k, stream)
+                            rerank_k, stream, row_mask)
 
     def train_from(self, index, row_ids, iters: int = 10) -> None:
         """k-means over the rows `row_ids` (sorted int64 numpy array) of a DeviceIndex."""

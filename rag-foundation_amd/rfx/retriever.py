@@ -12,7 +12,7 @@ import torch
 from . import filters
 from .batcher import GroupBatcher
 from .embedder import DEFAULT_MAX_TOKENS, DEFAULT_OVERLAP, Embedder, featurize_texts
-from .store import registry as default_registry
+from .store import ivf_filtered_mode, registry as default_registry
 from . import union as runion
 
 
@@ -243,7 +243,7 @@ class GpuRetriever:
         # a question over several stores: one scan of their union (rfx.union; RFX_UNION=0 disables)
         self.union = os.environ.get("RFX_UNION", "1") != "0"
         self.last_path = None  # "union" | "per-store" (tests, diagnostics)
-        self.last_filter_path = None  # "segmented" | "masked": how the last filtered batch was searched
+        self.last_filter_path = None  # "segmented" | "masked" | "ivf": how the last filtered batch was searched
         self.last_diversity = None  # "union" | "store" | None: where the last question was diversified
         self.last_hybrid = None  # "store" | None: the last question fused a dense and a lexical answer per store
 
@@ -314,23 +314,43 @@ class GpuRetriever:
             s, r = s.cpu().tolist(), r.cpu().tolist()
         return [(s[i][:k], r[i][:k]) for i, (_, k) in enumerate(items)]
 
+    @staticmethod
+    def _lists_possible(st) -> bool:
+        """RFX_IVF_FILTERED is on and the store has posting lists: its rule may send a plain filtered
+        question there (LocalStore.search_lists_filtered decides, per filter, when it runs)."""
+        return getattr(st, "ivf", None) is not None and hasattr(st, "search_lists_filtered") and \
+            ivf_filtered_mode() != "0"
+
     def _run_batch(self, name, metadata_filter, items):
         """Batch runner: resolves the store and its row mask when the batch runs (a batcher holds
-        no LocalStore, so a store that another process replaced or dropped is freed here too)."""
+        no LocalStore, so a store that another process replaced or dropped is freed here too).
+        A filtered batch of plain questions (none asks for diversity) takes an IVF store's posting lists
+        when the store's rule says so (RFX_IVF_FILTERED; LocalStore.search_filtered reports the path);
+        filtered diverse, hybrid and union-view questions keep the exact scan."""
         st = self.registry.get(name)
         if st is None:
             return [None] * len(items)
+        path = ["masked"]
         def run():
             mask = st.row_mask(metadata_filter) if metadata_filter is not None else None
             if metadata_filter is not None and mask is None:
                 return None
+            path[0] = "masked"
+            if mask is not None and all(len(it) == 2 for it in items) and self._lists_possible(st):
+                kmax = max(k for _, k in items)
+                with torch.cuda.device(st.device):
+                    q = self.embedder(st.dim).embed_texts([t for t, _ in items], st.dtype)
+                    s, r, p = st.search_filtered(q, kmax, metadata_filter)  # (the exact path = the masked search)
+                    s, r = s.tolist(), r.tolist()
+                path[0] = "ivf" if p == "ivf" else "masked"
+                return [(s[i][:k], r[i][:k]) for i, (_, k) in enumerate(items)]
             return self._search_store_batch(st, items, mask)
 
         res, gen = _numbered(st, run)
         if res is None:
             return [None] * len(items)
         if metadata_filter is not None:
-            self.last_filter_path = "masked"
+            self.last_filter_path = path[0]
         return [_answer(st, s, r, gen) for s, r in res]
 
     def _run_hybrid_batch(self, name, metadata_filter, items):
@@ -389,7 +409,10 @@ class GpuRetriever:
         by filter and each group's row ranges resolved (a filter that matches no file answers None); then
         ONE segmented search reads only the selected rows (DeviceIndex.search_segmented), or, when the
         filters select too much of the store for that to pay (segmented_max_fraction), one masked search
-        per distinct filter runs as before."""
+        per distinct filter runs as before.  On an IVF store under RFX_IVF_FILTERED, a group of plain
+        questions (no diversity) whose filter the store's rule sends to the posting lists is answered
+        there first (last_filter_path "ivf"); every other group goes through the choice above unchanged.
+        Filtered diverse, hybrid and union-view questions keep the exact scan."""
         st = self.registry.get(name)
         if st is None:
             return [None] * len(items)
@@ -406,6 +429,27 @@ class GpuRetriever:
             ranges = st.segment_ranges(filt)
             if ranges:
                 groups.append((filt, idxs, ranges))
+        rest = groups
+        if self._lists_possible(st):  # plain groups the store's rule sends to its posting lists
+            plain = [g for g in groups if all(len(items[i]) == 3 for i in g[1])]
+            rest = [g for g in groups if not all(len(items[i]) == 3 for i in g[1])]
+            if plain:
+                order = [i for _, idxs, _ in plain for i in idxs]
+                at = {i: p for p, i in enumerate(order)}
+                with torch.cuda.device(st.device):  # one embedding for all of them
+                    q_all = self.embedder(st.dim).embed_texts([items[i][0] for i in order], st.dtype)
+                    for g in plain:
+                        filt, idxs, _ = g
+                        q = q_all[[at[i] for i in idxs]].contiguous()
+                        res = st.search_lists_filtered(q, max(items[i][1] for i in idxs), filt)
+                        if res is None:  # the rule keeps this filter exact: the choice below, as ever
+                            rest.append(g)
+                            continue
+                        self.last_filter_path = "ivf"
+                        s, r = res[0].tolist(), res[1].tolist()
+                        for p, i in enumerate(idxs):
+                            out[i] = (st, s[p][:items[i][1]], r[p][:items[i][1]])
+        groups = rest
         if not groups:
             return out
         mode = segmented_mode()

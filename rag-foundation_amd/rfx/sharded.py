@@ -462,7 +462,10 @@ class ShardedIvf:
             for p, sh in zip(self.parts, self.sidx.shards):
                 p.add_from(sh, sh.rows)
 
-    def search_index(self, queries: torch.Tensor, k: int, nprobe: int, index=None, rerank_k: int = None, stream=None):
+    def search_index(self, queries: torch.Tensor, k: int, nprobe: int, index=None, rerank_k: int = None, stream=None,
+                     row_mask=None):
+        """row_mask: the per-shard list of masks ShardedIndex.search takes (mask_tensor); shard i's goes to
+        shard i's list scan, nothing else changes, so a filtered answer is the one-device answer too."""
         from .ivf import rerank_candidates
         sidx = self.sidx
         rk = max(int(k), 16) if rerank_k is None else int(rerank_k)
@@ -472,11 +475,12 @@ class ShardedIvf:
             nq = queries.shape[0]
             src = torch.cuda.current_stream(queries.device)
             qs, recs = [], []
-            for p, sh, base, d, st in zip(self.parts, sidx.shards, sidx.bases, sidx.devices, sidx._streams):
+            for i, (p, sh, base, d, st) in enumerate(zip(self.parts, sidx.shards, sidx.bases, sidx.devices,
+                                                         sidx._streams)):
                 st.wait_stream(src)
                 with torch.cuda.device(d), torch.cuda.stream(st):
                     q = queries.to(torch.device("cuda", d), non_blocking=True)
-                    s, r = p.search(q, rk, nprobe, stream=st)
+                    s, r = p.search(q, rk, nprobe, stream=st, row_mask=row_mask[i] if row_mask is not None else None)
                     recs.append(topk_merge_records(s, r, rk, row_offset=base, stream=st))
                 qs.append(q)
             cands = self._merge_each(sidx._exchange(recs, nq, rk, everywhere=True), rk)

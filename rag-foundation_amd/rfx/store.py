@@ -35,7 +35,8 @@ live rows once there are train_min of them (again at every 8x growth) and commit
 file with the manifest; every process keeps an IvfIndex (rfx.ivf) over the same rows in the same
 order, built from the committed centroids and extended incrementally as rows arrive.  Unfiltered
 searches probe nprobe lists and re-rank the candidates exactly against the DeviceIndex rows (so
-tombstones, NaN there, never return); filtered searches and untrained stores use the exact scan.
+tombstones, NaN there, never return); untrained stores use the exact scan, and so do filtered searches
+unless RFX_IVF_FILTERED sends them through the lists under a row mask (search_filtered).
 
 GPU state is a process-level singleton (StoreRegistry), because get_rag_client() builds a new
 adapter per request (chat.py:937, ingestion.py:214).
@@ -124,6 +125,34 @@ def index_spec_from_env():
     nlist = int(os.environ.get("RFX_IVF_NLIST", "1024"))
     return {"kind": "ivf", "nlist": nlist, "nprobe": min(int(os.environ.get("RFX_IVF_NPROBE", "32")), nlist, 64),
             "train_min": int(os.environ.get("RFX_IVF_TRAIN_MIN", str(32 * nlist)))}
+
+
+IVF_MAX_NPROBE = 64  # the C ABI's nprobe limit (rfx_ivf_search)
+
+
+def ivf_filtered_mode() -> str:
+    """RFX_IVF_FILTERED: "0" (default) = a filtered question of an IVF store runs the exact scan, "auto" =
+    it takes the posting lists when ivf_filter_nprobe's widened probe count fits the cap, "1" = always, at
+    the cap if need be.  Read at every question, as retriever.segmented_mode is."""
+    m = os.environ.get("RFX_IVF_FILTERED", "0").strip().lower()
+    return m if m in ("auto", "1") else "0"
+
+
+def ivf_filter_nprobe(nprobe, nlist, selected, live, mode):
+    """Probe count of a filtered IVF search, or None for the exact path.  A filter that keeps
+    `selected` of the `live` rows leaves a fixed nprobe scanning selected / live of the eligible rows an
+    unfiltered search scans, and recall falls with it; need = ceil(nprobe * live / selected) keeps the
+    expected number of eligible rows scanned at the unfiltered search's.  cap = min(64, nlist).
+    mode "auto": need when need <= cap, else None (the exact path's segmented form reads only the selected
+    rows); "1": min(need, cap); "0", or selected == 0: None."""
+    nprobe, nlist, selected, live = int(nprobe), int(nlist), int(selected), int(live)
+    if mode not in ("auto", "1") or selected <= 0:
+        return None
+    need = -(-nprobe * live // selected)
+    cap = min(IVF_MAX_NPROBE, nlist)
+    if mode == "1":
+        return min(need, cap)
+    return need if need <= cap else None
 
 
 def default_root() -> str:
@@ -857,7 +886,8 @@ class LocalStore:
     def search(self, queries, k, row_mask=None):
         """(scores, rows) of the top-k rows per query.  An IVF store with trained lists answers
         unfiltered searches from its lists (nprobe probes, exact re-rank of min(64, max(16, 2k))
-        candidates); otherwise, and under a metadata filter, the exact scan runs."""
+        candidates); otherwise, and under a metadata filter, the exact scan runs (search_filtered is the
+        entry that may take the lists under a filter, RFX_IVF_FILTERED)."""
         if row_mask is None and self.ivf is not None:
             with self.lock:  # the re-rank reads the DeviceIndex rows in place: no append meanwhile
                 if self.ivf_ready():
@@ -865,6 +895,54 @@ class LocalStore:
                                                  rerank_k=min(64, max(16, 2 * int(k))))
                     return s.cpu(), r.cpu()
         return self.index.search(queries, k, row_mask=row_mask)
+
+    def filtered_nprobe(self, metadata_filter):
+        """The probe count at which a question under this filter takes the posting lists, or None when it
+        takes the exact scan: ivf_filter_nprobe under RFX_IVF_FILTERED over the filter's selected rows
+        (the sum of mask_ranges) and the live rows; None too for a flat store or lists that are behind."""
+        mode = ivf_filtered_mode()
+        if mode == "0" or self.ivf is None:
+            return None
+        with self.lock:
+            if not self.ivf_ready():
+                return None
+            selected = sum(n for _, n in self.mask_ranges(metadata_filter))
+            live = len(self.rows) - self.dead_rows()
+            return ivf_filter_nprobe(self.spec["nprobe"], self.spec["nlist"], selected, live, mode)
+
+    def search_lists_filtered(self, queries, k, metadata_filter):
+        """The filtered search through the posting lists, or None when the rule (filtered_nprobe) keeps this
+        filter on the exact path: (scores, rows) on the host.  The rule, the mask and the search are one
+        evaluation under self.lock — as the unfiltered IVF search, the re-rank reads the DeviceIndex rows in
+        place."""
+        if ivf_filtered_mode() == "0" or self.ivf is None:
+            return None
+        with self.lock:
+            nprobe = self.filtered_nprobe(metadata_filter)
+            if nprobe is None:
+                return None
+            s, r = self.ivf.search_index(queries, k, nprobe, self.index, rerank_k=min(64, max(16, 2 * int(k))),
+                                         row_mask=self.row_mask(metadata_filter))
+            return s.cpu(), r.cpu()
+
+    def search_filtered(self, queries, k, metadata_filter):
+        """(scores, rows, path) of the top-k rows per query among the rows the filter selects, scores and rows
+        always on the host.  path "ivf": the posting lists at filtered_nprobe's widened probe count, the row
+        mask applied inside the list scan, exact re-rank of min(64, max(16, 2k)) candidates (DESIGN §4.15;
+        RFX_IVF_FILTERED=auto|1).  path "exact": the masked exact scan — the default, a probe count past the
+        cap under auto, lists that are behind, a flat store.  A filter that matches no file answers padding
+        (-inf, -1)."""
+        import torch
+        mask = self.row_mask(metadata_filter)
+        if mask is None:
+            nq = queries.shape[0]
+            return (torch.full((nq, k), float("-inf"), dtype=torch.float32),
+                    torch.full((nq, k), -1, dtype=torch.int64), "exact")
+        out = self.search_lists_filtered(queries, k, metadata_filter)
+        if out is not None:
+            return out[0], out[1], "ivf"
+        s, r = self.index.search(queries, k, row_mask=mask)
+        return s.cpu(), r.cpu(), "exact"
 
     def row_mask(self, metadata_filter):
         """Device row mask (int32 words) of the live files whose upload metadata matches the
