@@ -482,6 +482,33 @@ int rfx_ivf_search_rerank_masked(rfx_ivf_t h, const void* queries_d, int64_t nq,
                                  int nprobe, int rerank_k, const void* rows_d, int rows_dtype,
                                  const uint32_t* row_mask_d, int64_t mask_words, float* out_scores_d,
                                  int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream);
+/* One list search for a batch of questions under DIFFERENT filters: behind ask_stream every
+ * tenant's question carries its own metadata_filter (gemini_rag.py:463-469,517-551), and the store's one batcher
+ * hands them over together.  masks_d: a DEVICE array of n_masks device pointers to row bitmaps in the format
+ * above, each of at least mask_words words (the store's cached masks; they are not copied or concatenated);
+ * mask_of_d [nq] (device, int32): question q's index into the table, -1 = no mask; nprobe_of_d [nq] (device,
+ * int32): question q's probe count, 1 <= nprobe_of[q] <= nprobe_max <= min(64, nlist).  Question q's answer is,
+ * bit for bit, what rfx_ivf_search_masked returns for question q alone at nprobe_of[q] under its own mask
+ * (rfx_ivf_search where mask_of[q] == -1).  Workspaces: the existing size queries at nprobe_max.
+ * RFX_EINVAL, before anything is launched: mask_words < (rows + 31) / 32 (n_masks > 0); a mask_of entry outside
+ * [-1, n_masks) — n_masks == 0 with an entry >= 0 included; an nprobe_of entry outside [1, nprobe_max].  With
+ * n_masks == 0 no mask is ever read and mask_words is not looked at.  The two arrays are checked on the host:
+ * mask_of_h / nprobe_of_h are the caller's host copies of them (both or neither; the contract is that they hold
+ * what the device arrays hold when the kernels run), read during the call only.  With either NULL the device
+ * arrays are read back instead (2 * nq * 4 bytes and one wait on `stream`: the call then cannot be captured into a
+ * graph, and both arrays must have been written on `stream` or before).  The re-rank form masks its candidate
+ * search only. */
+int rfx_ivf_search_multi(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k,
+                         const uint32_t* const* masks_d, int n_masks, int64_t mask_words,
+                         const int32_t* mask_of_d, const int32_t* nprobe_of_d, int nprobe_max,
+                         const int32_t* mask_of_h, const int32_t* nprobe_of_h, float* out_scores_d,
+                         int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream);
+int rfx_ivf_search_rerank_multi(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int rerank_k,
+                                const void* rows_d, int rows_dtype, const uint32_t* const* masks_d, int n_masks,
+                                int64_t mask_words, const int32_t* mask_of_d, const int32_t* nprobe_of_d,
+                                int nprobe_max, const int32_t* mask_of_h, const int32_t* nprobe_of_h,
+                                float* out_scores_d, int64_t* out_rows_d, void* ws_d, size_t ws_bytes,
+                                void* stream);
 /* The re-rank step alone, for a store row-sharded over several devices (rfx/sharded.py
  * ShardedIvf; gemini_rag.py:463-469's file-search tool over an RFX_INDEX=ivf store): cand_d
  * [nq][n_cand] holds GLOBAL row ids (< 0 = padding); the candidates in [row_lo, row_lo + n_rows)

@@ -402,21 +402,63 @@ int rfx_ivf_search_workspace_bytes(rfx_ivf_t h, int64_t nq, int k, int nprobe, s
   return RFX_OK;
 }
 
-// The one body of rfx_ivf_search and rfx_ivf_search_masked (row_mask_d == nullptr: unmasked).
+// The per-question arguments of rfx_ivf_search_multi / rfx_ivf_search_rerank_multi; the probe
+// count the body takes is then nprobe_max, the stride of every per-pair array.
+struct IvfMulti {
+  const uint32_t* const* masks_d;
+  int n_masks;
+  const int32_t* mask_of_d;
+  const int32_t* nprobe_of_d;
+  const int32_t* mask_of_h;  // the caller's host copies of the two arrays (both or neither): what is checked
+  const int32_t* nprobe_of_h;
+};
+
+// The one body of rfx_ivf_search, rfx_ivf_search_masked (row_mask_d == nullptr: unmasked) and rfx_ivf_search_multi
+// (mu != nullptr: a mask and a probe count per question; row_mask_d is then unused, mask_words the length of
+// every mask of the table).
 static int ivf_search(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe,
                       const uint32_t* row_mask_d, int64_t mask_words, float* out_scores_d, int64_t* out_rows_d, void* ws_d,
-                      size_t ws_bytes, void* stream) {
+                      size_t ws_bytes, void* stream, const IvfMulti* mu = nullptr) {
   auto iv = get(h);
   if (!iv) return api_fail(RFX_EINVAL, "unknown IVF handle");
   if (!valid_dtype(dtype)) return api_fail(RFX_EINVAL, "bad query dtype");
   IvfLayout L;
   int rc = ivf_layout(*iv, nq, k, nprobe, L);
   if (rc) return rc;
+  if (mu && (mu->n_masks < 0 || (mu->n_masks > 0 && !mu->masks_d)))
+    return api_fail(RFX_EINVAL, "n_masks=%d with a null mask table", mu->n_masks);
   if (nq == 0) return RFX_OK;
   if (!queries_d || !out_scores_d || !out_rows_d) return api_fail(RFX_EINVAL, "null queries / outputs");
+  if (mu && (!mu->mask_of_d || !mu->nprobe_of_d)) return api_fail(RFX_EINVAL, "null mask_of / nprobe_of");
   if (!ws_d || ws_bytes < L.total) return api_fail(RFX_EINVAL, "workspace too small (%zu < %zu)", ws_bytes, L.total);
   std::lock_guard<std::mutex> lk(iv->mu);
   if (!iv->trained) return api_fail(RFX_EINVAL, "IVF index not trained");
+  if (mu) {
+    // The kernels index the mask table by mask_of and the pair slots by nprobe_of: both are checked here, before
+    // anything is launched — on the host copies the caller passes (no wait on the stream, the call stays
+    // capturable), else on a read-back of the device arrays (2 * nq * 4 bytes and one wait on the stream).
+    std::vector<int32_t> hv;
+    const int32_t *mo = mu->mask_of_h, *no = mu->nprobe_of_h;
+    if (!mo || !no) {
+      IVF_HIP(hipSetDevice(iv->device));
+      hv.resize(2 * (size_t)nq);
+      IVF_HIP(hipMemcpyAsync(hv.data(), mu->mask_of_d, (size_t)nq * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+      IVF_HIP(hipMemcpyAsync(hv.data() + nq, mu->nprobe_of_d, (size_t)nq * 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
+      IVF_HIP(hipStreamSynchronize((hipStream_t)stream));
+      mo = hv.data(), no = hv.data() + nq;
+    }
+    for (int64_t q = 0; q < nq; ++q) {
+      const int32_t m = mo[q], np = no[q];
+      if (m >= 0 && mu->n_masks == 0) return api_fail(RFX_EINVAL, "mask_of[%lld]=%d but n_masks is 0", (long long)q, m);
+      if (m < -1 || m >= mu->n_masks)
+        return api_fail(RFX_EINVAL, "mask_of[%lld]=%d out of range [-1, n_masks=%d)", (long long)q, m, mu->n_masks);
+      if (np < 1 || np > nprobe)
+        return api_fail(RFX_EINVAL, "nprobe_of[%lld]=%d out of range [1, nprobe_max=%d]", (long long)q, np, nprobe);
+    }
+  }
+  if (mu && mu->n_masks > 0 && mask_words < (iv->rows + 31) / 32)
+    return api_fail(RFX_EINVAL, "row mask has %lld words, the index needs %lld", (long long)mask_words,
+                    (long long)((iv->rows + 31) / 32));
   // every row id the scan looks up is below iv->rows, so this is the bound of the mask reads
   if (row_mask_d && mask_words < (iv->rows + 31) / 32)
     return api_fail(RFX_EINVAL, "row mask has %lld words, the index needs %lld", (long long)mask_words,
@@ -438,13 +480,19 @@ static int ivf_search(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype,
   rfx::ivf::launch_quantize(queries_d, nq, iv->dim, dtype, qq, qinv, st);
   if (rfx::ivf::launch_coarse_scores(qq, nq, iv->qc, iv->nlist, iv->dim, iv->fc, S, Sid, st))
     return api_fail(RFX_EUNSUPPORTED, "coarse scoring launch rejected");
-  if (rfx::ivf::launch_probe_select(S, nq, iv->nlist, nprobe, ps, pid, st) != 0 &&
+  // (the merge's output is sorted (score desc, id asc), so its first nprobe_of[q] of the nprobe_max are question
+  // q's own selection; probe_select's is in no order and selects per question)
+  if (rfx::ivf::launch_probe_select(S, nq, iv->nlist, nprobe, ps, pid, st, mu ? mu->nprobe_of_d : nullptr) != 0 &&
       rfx::launch_topk_merge(S, Sid, 0, nq, iv->nlist, nprobe, 0, ps, pid, st))
     return api_fail(RFX_EUNSUPPORTED, "probe selection rejected (nprobe=%d)", nprobe);
-  if (rfx::ivf::launch_group_pairs(pid, (int)(nq * nprobe), iv->nlist, poff, pairs, st))
+  if (mu)  // the slots j >= nprobe_of[q]: marked, their candidates set empty on every call
+    rfx::ivf::launch_absent_pairs(mu->nprobe_of_d, nq, nprobe, L.splits * 4 * L.K, pid, ps, cs, cr, st);
+  if (rfx::ivf::launch_group_pairs(pid, (int)(nq * nprobe), iv->nlist, poff, pairs, st, mu != nullptr))
     return api_fail(RFX_EUNSUPPORTED, "pair grouping rejected");
-  if (rfx::ivf::launch_list_scan(L.K, iv->dim, iv->nlist, L.splits, iv->lcodes, iv->linv, iv->lids, iv->off, poff, pairs, nprobe,
-                                 qq, qinv, cs, cr, row_mask_d, st))
+  if (mu ? rfx::ivf::launch_list_scan_multi(L.K, iv->dim, iv->nlist, L.splits, iv->lcodes, iv->linv, iv->lids, iv->off, poff,
+                                            pairs, nprobe, qq, qinv, cs, cr, mu->masks_d, mu->mask_of_d, st)
+         : rfx::ivf::launch_list_scan(L.K, iv->dim, iv->nlist, L.splits, iv->lcodes, iv->linv, iv->lids, iv->off, poff, pairs,
+                                      nprobe, qq, qinv, cs, cr, row_mask_d, st))
     return api_fail(RFX_EUNSUPPORTED, "list scan launch rejected (k=%d dim=%d)", k, iv->dim);
   // (the wave lists are sorted best first, empty slots last: the merge reads each only as far as it can
   // still admit)
@@ -487,7 +535,8 @@ int rfx_ivf_rerank_workspace_bytes(rfx_ivf_t h, int64_t nq, int k, int nprobe, i
 // only (the re-rank's candidates are eligible rows already).
 static int ivf_search_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe, int rerank_k,
                              const void* rows_d, int rows_dtype, const uint32_t* row_mask_d, int64_t mask_words,
-                             float* out_scores_d, int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream) {
+                             float* out_scores_d, int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream,
+                             const IvfMulti* mu = nullptr) {
   auto iv = get(h);
   if (!iv) return api_fail(RFX_EINVAL, "unknown IVF handle");
   if (!valid_dtype(rows_dtype) || !valid_dtype(dtype)) return api_fail(RFX_EINVAL, "bad dtype");
@@ -503,7 +552,8 @@ static int ivf_search_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, int
   int64_t* cr = (int64_t*)(ws + al256(ivf) + al256((size_t)nq * rerank_k * 8));
   float* rs = (float*)(ws + al256(ivf) + 2 * al256((size_t)nq * rerank_k * 8));
   int64_t* rr = cr;  // the re-rank kernel rewrites rows in place (padding -> empty sentinel)
-  if ((rc = ivf_search(h, queries_d, nq, dtype, rerank_k, nprobe, row_mask_d, mask_words, cs, cr, ws, al256(ivf), stream)))
+  if ((rc = ivf_search(h, queries_d, nq, dtype, rerank_k, nprobe, row_mask_d, mask_words, cs, cr, ws, al256(ivf), stream,
+                       mu)))
     return rc;
   hipStream_t st = (hipStream_t)stream;
   IVF_HIP(hipSetDevice(iv->device));
@@ -528,6 +578,27 @@ int rfx_ivf_search_rerank_masked(rfx_ivf_t h, const void* queries_d, int64_t nq,
                                  size_t ws_bytes, void* stream) {
   return ivf_search_rerank(h, queries_d, nq, dtype, k, nprobe, rerank_k, rows_d, rows_dtype, row_mask_d, mask_words,
                            out_scores_d, out_rows_d, ws_d, ws_bytes, stream);
+}
+
+// One list search for a batch under different filters (include/rfx.h).
+int rfx_ivf_search_multi(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k,
+                         const uint32_t* const* masks_d, int n_masks, int64_t mask_words, const int32_t* mask_of_d,
+                         const int32_t* nprobe_of_d, int nprobe_max, const int32_t* mask_of_h,
+                         const int32_t* nprobe_of_h, float* out_scores_d, int64_t* out_rows_d, void* ws_d,
+                         size_t ws_bytes, void* stream) {
+  const IvfMulti mu{masks_d, n_masks, mask_of_d, nprobe_of_d, mask_of_h, nprobe_of_h};
+  return ivf_search(h, queries_d, nq, dtype, k, nprobe_max, nullptr, mask_words, out_scores_d, out_rows_d, ws_d, ws_bytes,
+                    stream, &mu);
+}
+
+int rfx_ivf_search_rerank_multi(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int rerank_k,
+                                const void* rows_d, int rows_dtype, const uint32_t* const* masks_d, int n_masks,
+                                int64_t mask_words, const int32_t* mask_of_d, const int32_t* nprobe_of_d, int nprobe_max,
+                                const int32_t* mask_of_h, const int32_t* nprobe_of_h, float* out_scores_d,
+                                int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream) {
+  const IvfMulti mu{masks_d, n_masks, mask_of_d, nprobe_of_d, mask_of_h, nprobe_of_h};
+  return ivf_search_rerank(h, queries_d, nq, dtype, k, nprobe_max, rerank_k, rows_d, rows_dtype, nullptr, mask_words,
+                           out_scores_d, out_rows_d, ws_d, ws_bytes, stream, &mu);
 }
 
 // The re-rank step alone over one shard's rows (rfx/sharded.py ShardedIvf): candidates are global

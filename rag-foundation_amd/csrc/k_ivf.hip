@@ -511,7 +511,10 @@ int launch_build_lists(const int* labels, int64_t n, int m, const int8_t* codes,
 
 // ---- search: (query, probe) pairs grouped by list ---------------------------------------------------
 // pair p = q * nprobe + j probes list probes[p]; out: pair_off[0..m] (CSR by list), pairs[].
+// SKIP (a probe count per question): probes[p] < 0 marks a slot j >= nprobe_of[q]; such a pair is
+// in no list.  SKIP = false is the code it was.
 constexpr int kMaxListsGroup = 16384;
+template <bool SKIP>
 __global__ __launch_bounds__(1024) void group_pairs_kernel(const int64_t* __restrict__ probes, int P, int m,
                                                            int* __restrict__ pair_off, int* __restrict__ pairs) {
   __shared__ int cnt[kMaxListsGroup];
@@ -519,7 +522,12 @@ __global__ __launch_bounds__(1024) void group_pairs_kernel(const int64_t* __rest
   const int t = threadIdx.x;
   for (int i = t; i < m; i += 1024) cnt[i] = 0;
   __syncthreads();
-  for (int p = t; p < P; p += 1024) atomicAdd(&cnt[(int)probes[p]], 1);
+  for (int p = t; p < P; p += 1024) {
+    if constexpr (SKIP) {
+      if (probes[p] < 0) continue;
+    }
+    atomicAdd(&cnt[(int)probes[p]], 1);
+  }
   __syncthreads();
   const int per = (m + 1023) / 1024;
   const int b = t * per, e = min(m, b + per);
@@ -542,7 +550,12 @@ __global__ __launch_bounds__(1024) void group_pairs_kernel(const int64_t* __rest
   }
   if (t == 1023) pair_off[m] = part[1023];
   __syncthreads();
-  for (int p = t; p < P; p += 1024) pairs[atomicAdd(&cnt[(int)probes[p]], 1)] = p;
+  for (int p = t; p < P; p += 1024) {
+    if constexpr (SKIP) {
+      if (probes[p] < 0) continue;
+    }
+    pairs[atomicAdd(&cnt[(int)probes[p]], 1)] = p;
+  }
 }
 
 // Posting-list scan.  Grid (list, split): block (L, s) takes the 64-row groups s*4 + w,
@@ -768,6 +781,173 @@ __global__ __launch_bounds__(256) void list_scan_kernel(const int8_t* __restrict
   }
 }
 
+// A mask per question.  list_scan_kernel above stays textually what it was,
+// so its twelve <K, NC, false> and twelve <K, NC, true> instantiations are the parent's code; this is its body
+// again with the row's eligibility per question of the staged batch.  masks is a device table of the store's
+// row bitmaps, mask_of[q] question q's index into it (-1: no mask).  Eligibility is a bit per staged question in
+// the lane's okm and goes where `ok` goes above: NaN among the seed chunks, valid = false in offer(); a
+// past-the-end lane is ineligible for every question.  The staged questions' mask indices are wave-uniform, and
+// the batch is put in ascending mask order first (an odd-even transposition network over <= 8 scalars, once per
+// batch), so the lane reloads its mask word only where the index changes from one staged question to the next —
+// a scalar branch; a batch under one mask costs one 4-byte load per row, as MASKED, and questions without a mask
+// come first and cost none.  Nothing depends on the order of a list's pairs (group_pairs_kernel's cursor is an
+// atomic): the candidates go out by pair number.
+template <int K, int NC>
+__global__ __launch_bounds__(256) void list_scan_multi_kernel(
+    const int8_t* __restrict__ codes, const float* __restrict__ inv, const int* __restrict__ ids,
+    const int64_t* __restrict__ off, const int* __restrict__ pair_off, const int* __restrict__ pairs, int nprobe,
+    const int8_t* __restrict__ qq, const float* __restrict__ qinv, float* __restrict__ cand_s, int* __restrict__ cand_r,
+    const uint32_t* const* __restrict__ masks, const int* __restrict__ mask_of) {
+  constexpr int D = NC * 256, NCH = D / 16;  // 16-B chunks per row
+  // Round 6: one lane per row.  The codes are in 64-row blocks, chunk-major (gather_rows_kernel), so a wave's
+  // load of chunk c of its 64 rows is one 1-KB run; the batch's queries are wave-uniform and come through
+  // scalar loads (SGPR operands of v_dot4), so no LDS reads, and every lane ends with its row's whole dot
+  // for each query (no cross-lane sums).  Before, 16 lanes shared a row: per 4 rows a wave read 8 KB of
+  // staged queries from LDS and summed 8 dots over 16 lanes (DPP), the list scan at 5.3 TB/s.
+  constexpr int G = 4;  // chunks per load group (double-buffered)
+  static_assert(NCH % G == 0, "chunk groups");
+  constexpr int NG = NCH / G;
+  __shared__ float qf[kQB];
+  const int L = blockIdx.x, S = gridDim.y, sp = blockIdx.y;
+  const int p0 = pair_off[L], p1 = pair_off[L + 1];
+  if (p0 == p1) return;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int64_t r0 = off[L], r1 = off[L + 1];
+  for (int pb = p0; pb < p1; pb += kQB) {
+    const int nb = min(kQB, p1 - pb);
+    const uint4* qv[kQB];
+    int pr[kQB], mk[kQB];     // the staged pairs and their mask indices (wave-uniform), in mask order
+    const uint32_t* mp[kQB];  // the masks' words (nullptr: no mask)
+    {
+#pragma unroll
+      for (int qi = 0; qi < kQB; ++qi) {
+        pr[qi] = __builtin_amdgcn_readfirstlane(pairs[pb + (qi < nb ? qi : 0)]);
+        mk[qi] = qi < nb ? __builtin_amdgcn_readfirstlane(mask_of[pr[qi] / nprobe]) : 0x7fffffff;
+      }
+#pragma unroll
+      for (int r = 0; r < kQB; ++r)  // odd-even transposition: ascending mask index, the padding last
+#pragma unroll
+        for (int i = r & 1; i + 1 < kQB; i += 2)
+          if (mk[i] > mk[i + 1]) {
+            const int tm = mk[i], tp = pr[i];
+            mk[i] = mk[i + 1], pr[i] = pr[i + 1];
+            mk[i + 1] = tm, pr[i + 1] = tp;
+          }
+#pragma unroll
+      for (int qi = 0; qi < kQB; ++qi) {
+        mp[qi] = qi < nb && mk[qi] >= 0 ? masks[mk[qi]] : nullptr;
+        qv[qi] = (const uint4*)(qq + (int64_t)(pr[qi] / nprobe) * D);
+      }
+      if (tid == 0) {
+#pragma unroll
+        for (int qi = 0; qi < kQB; ++qi) qf[qi] = qi < nb ? qinv[pr[qi] / nprobe] : 0.f;
+      }
+    }
+    __syncthreads();
+    WaveList<K> lst[kQB];
+#pragma unroll
+    for (int qi = 0; qi < kQB; ++qi) lst[qi].init();
+    // Round 6: a wave's first kSeedChunks 64-row chunks are kept in registers (score per lane, chunk and
+    // query; the id per lane and chunk) and seed each query's sorted list by one selection (seed_lists), the
+    // later chunks go through the list inserts.  A config-5 wave streams ~3 chunks of a list per batch, so the
+    // inserts of its first chunks — nearly every candidate, the list still empty — were most of them.
+    float ka[kQB][kSeedChunks];
+    int kg[kSeedChunks];
+    int nch = 0;  // chunks this wave has scored in this batch (wave-uniform)
+#pragma unroll
+    for (int c = 0; c < kSeedChunks; ++c) {
+#pragma unroll
+      for (int qi = 0; qi < kQB; ++qi) ka[qi][c] = __builtin_nanf("");
+      kg[c] = kEmptyRow;
+    }
+    for (int64_t base = r0 + (int64_t)(sp * 4 + w) * 64; base < r1; base += 256 * S) {
+      const int64_t crow = base + lane;
+      const bool valid = crow < r1;
+      const int64_t cr = valid ? crow : r0;  // in-list row (never past the list)
+      const int8_t* rp = codes + (cr >> 6) * (64 * D) + (cr & 63) * 16;  // chunk c at rp + c * 1024
+      int acc[kQB];
+#pragma unroll
+      for (int qi = 0; qi < kQB; ++qi) acc[qi] = 0;
+      uint4 va[G], vb[G];
+#pragma unroll
+      for (int c = 0; c < G; ++c) va[c] = *(const uint4*)(rp + c * 1024);
+#pragma unroll
+      for (int cg = 0; cg < NG; ++cg) {
+        uint4(&cur)[G] = (cg & 1) ? vb : va;
+        uint4(&nxt)[G] = (cg & 1) ? va : vb;
+        if (cg + 1 < NG) {
+#pragma unroll
+          for (int c = 0; c < G; ++c) nxt[c] = *(const uint4*)(rp + ((cg + 1) * G + c) * 1024);
+        }
+#pragma unroll
+        for (int qi = 0; qi < kQB; ++qi) {
+          if (qi < nb) {
+#pragma unroll
+            for (int c = 0; c < G; ++c) {
+              const uint4 q = qv[qi][cg * G + c];
+              acc[qi] = __builtin_amdgcn_sdot4((int)cur[c].x, (int)q.x, acc[qi], false);
+              acc[qi] = __builtin_amdgcn_sdot4((int)cur[c].y, (int)q.y, acc[qi], false);
+              acc[qi] = __builtin_amdgcn_sdot4((int)cur[c].z, (int)q.z, acc[qi], false);
+              acc[qi] = __builtin_amdgcn_sdot4((int)cur[c].w, (int)q.w, acc[qi], false);
+            }
+          }
+        }
+      }
+      float cand[kQB];  // |dot| <= 768 * 127 * 127 < 2^24: exact in f32, the value the 16-lane sum had
+#pragma unroll
+      for (int qi = 0; qi < kQB; ++qi) cand[qi] = (float)acc[qi];
+      const float ir = inv[cr];
+      const int gid = ids[cr];
+      uint32_t okm = 0u;  // bit qi = the row may take a slot of staged question qi's list
+      {
+        // gid < rows <= 32 * mask words of every table entry (checked by the caller); a past-the-end lane
+        // looks up its list's first row and is cleared below
+        const uint32_t wi = (uint32_t)gid >> 5, bi = (uint32_t)gid & 31u;
+        uint32_t word = 0xffffffffu;  // mask index -1: every row
+        int cur = -1;
+#pragma unroll
+        for (int qi = 0; qi < kQB; ++qi)
+          if (qi < nb) {
+            if (mk[qi] != cur) {  // wave-uniform
+              cur = mk[qi];
+              word = mp[qi][wi];
+            }
+            okm |= ((word >> bi) & 1u) << qi;
+          }
+        okm = valid ? okm : 0u;
+      }
+      auto okq = [&](int qi) { return ((okm >> qi) & 1u) != 0u; };
+      if (nch < kSeedChunks) {
+#pragma unroll
+        for (int c = 0; c < kSeedChunks; ++c)
+          if (c == nch) {
+#pragma unroll
+            for (int qi = 0; qi < kQB; ++qi)
+              ka[qi][c] = okq(qi) && qi < nb ? __fmul_rn(cand[qi], __fmul_rn(ir, qf[qi])) : __builtin_nanf("");
+            kg[c] = gid;
+          }
+        if (++nch == kSeedChunks) seed_lists<K, kQB, kSeedChunks>(ka, kg, lst, w);
+      } else {
+#pragma unroll
+        for (int qi = 0; qi < kQB; ++qi)
+          if (qi < nb) lst[qi].offer(__fmul_rn(cand[qi], __fmul_rn(ir, qf[qi])), gid, okq(qi));
+      }
+    }
+    if (nch < kSeedChunks) seed_lists<K, kQB, kSeedChunks>(ka, kg, lst, w);  // (fewer chunks than kept)
+    if (lane < K) {
+#pragma unroll
+      for (int qi = 0; qi < kQB; ++qi) {
+        if (qi < nb) {
+          const int64_t o = (((int64_t)pr[qi] * S + sp) * 4 + w) * K + lane;
+          cand_s[o] = lst[qi].ls;
+          cand_r[o] = lst[qi].lr;
+        }
+      }
+    }
+    __syncthreads();  // qf is rewritten by the next batch
+  }
+}
+
 int list_k(int k) { return k <= 4 ? 4 : (k <= 16 ? 16 : (k <= 64 ? 64 : -1)); }
 
 int launch_list_scan(int K, int D, int m, int splits, const int8_t* codes, const float* inv, const int* ids, const int64_t* off,
@@ -790,6 +970,23 @@ int launch_list_scan(int K, int D, int m, int splits, const int8_t* codes, const
   return -1;
 }
 
+int launch_list_scan_multi(int K, int D, int m, int splits, const int8_t* codes, const float* inv, const int* ids,
+                           const int64_t* off, const int* pair_off, const int* pairs, int nprobe, const int8_t* qq,
+                           const float* qinv, float* cs, int* cr, const uint32_t* const* masks, const int* mask_of,
+                           hipStream_t st) {
+#define RFX_LS(KV, NCV)                                                                                              \
+  if (K == KV && D == NCV * 256) {                                                                                   \
+    hipLaunchKernelGGL((list_scan_multi_kernel<KV, NCV>), dim3(m, splits), dim3(256), 0, st, codes, inv, ids, off,   \
+                       pair_off, pairs, nprobe, qq, qinv, cs, cr, masks, mask_of);                                   \
+    return 0;                                                                                                        \
+  }
+  RFX_LS(4, 1) RFX_LS(4, 2) RFX_LS(4, 3) RFX_LS(4, 4)
+  RFX_LS(16, 1) RFX_LS(16, 2) RFX_LS(16, 3) RFX_LS(16, 4)
+  RFX_LS(64, 1) RFX_LS(64, 2) RFX_LS(64, 3) RFX_LS(64, 4)
+#undef RFX_LS
+  return -1;
+}
+
 // ---- probe selection: each query's nprobe best coarse scores (round 6) ----------------------------
 // One 256-thread block per query, up to kProbeMaxLists scores held in registers (16 per thread, list
 // c = tid + 256 i).  v = the nprobe-th largest orderable score by a bitwise search on block-wide ballot
@@ -798,14 +995,21 @@ int launch_list_scan(int K, int D, int m, int splits, const int8_t* codes, const
 // order (the pairs are grouped by list next, and every later step is order-free).  A coarse score is never -0.0
 // (f32(dot) * f_c: f_c is 0 only for an all-zero centroid, whose dot is 0, and otherwise >= 1 / (127 * 32), far
 // from underflow), so ord_f32's order is the float order here, unlike in seed_lists.
+// PERQ: question q selects exactly its own nprobe_of[q] best (the writes are in no order, so the
+// first n of a wider selection could not stand in); nprobe stays the stride of ps / pid.  The slots past the
+// count are marked by absent_pairs_kernel.  PERQ = false never reads nprobe_of.
 constexpr int kProbeMaxLists = 4096;
+template <bool PERQ>
 __global__ __launch_bounds__(256) void probe_select_kernel(const float* __restrict__ S, int m, int nprobe,
-                                                           float* __restrict__ ps, int64_t* __restrict__ pid) {
+                                                           float* __restrict__ ps, int64_t* __restrict__ pid,
+                                                           const int* __restrict__ nprobe_of) {
   constexpr int PT = kProbeMaxLists / 256;
   __shared__ int wc[2][4];
   __shared__ int npos;
   const int tid = threadIdx.x, w = tid >> 6;
   const int64_t q = blockIdx.x;
+  const int stride = nprobe;
+  if constexpr (PERQ) nprobe = nprobe_of[q];
   uint32_t key[PT];
 #pragma unroll
   for (int i = 0; i < PT; ++i) {
@@ -846,22 +1050,57 @@ __global__ __launch_bounds__(256) void probe_select_kernel(const float* __restri
     const bool keep = c < m && (key[i] > v || (key[i] == v && (uint32_t)c <= g2));
     if (keep) {
       const int o = atomicAdd(&npos, 1);
-      ps[q * nprobe + o] = S[q * m + c];
-      pid[q * nprobe + o] = c;
+      ps[q * stride + o] = S[q * m + c];
+      pid[q * stride + o] = c;
     }
   }
 }
 
-int launch_probe_select(const float* S, int64_t nq, int m, int nprobe, float* ps, int64_t* pid, hipStream_t st) {
+int launch_probe_select(const float* S, int64_t nq, int m, int nprobe, float* ps, int64_t* pid, hipStream_t st,
+                        const int* nprobe_of) {
   if (m > kProbeMaxLists || nprobe < 1 || nprobe > m || nq <= 0) return -1;
-  hipLaunchKernelGGL(probe_select_kernel, dim3((unsigned)nq), dim3(256), 0, st, S, m, nprobe, ps, pid);
+  if (nprobe_of)
+    hipLaunchKernelGGL(probe_select_kernel<true>, dim3((unsigned)nq), dim3(256), 0, st, S, m, nprobe, ps, pid, nprobe_of);
+  else
+    hipLaunchKernelGGL(probe_select_kernel<false>, dim3((unsigned)nq), dim3(256), 0, st, S, m, nprobe, ps, pid, nullptr);
   return 0;
 }
 
-int launch_group_pairs(const int64_t* probes, int P, int m, int* pair_off, int* pairs, hipStream_t st) {
+int launch_group_pairs(const int64_t* probes, int P, int m, int* pair_off, int* pairs, hipStream_t st, bool skip) {
   if (m > kMaxListsGroup) return -1;
-  hipLaunchKernelGGL(group_pairs_kernel, dim3(1), dim3(1024), 0, st, probes, P, m, pair_off, pairs);
+  if (skip)
+    hipLaunchKernelGGL(group_pairs_kernel<true>, dim3(1), dim3(1024), 0, st, probes, P, m, pair_off, pairs);
+  else
+    hipLaunchKernelGGL(group_pairs_kernel<false>, dim3(1), dim3(1024), 0, st, probes, P, m, pair_off, pairs);
   return 0;
+}
+
+// ---- a probe count per question: the slots and candidates of the pairs that do not exist ----
+// Block (q, j) with j >= nprobe_of[q]: probes[q * nprobe + j] = -1 (group_pairs_kernel<true> skips it) and the
+// pair's splits * 4 * K candidate slots are set empty (-inf, kEmptyRow) — no list-scan block writes them, the
+// final merge reads every slot of every question, and the workspace still holds whatever an earlier, wider call
+// left there.
+__global__ __launch_bounds__(256) void absent_pairs_kernel(const int* __restrict__ nprobe_of, int nprobe, int per_pair,
+                                                           int64_t* __restrict__ pid, float* __restrict__ ps,
+                                                           float* __restrict__ cand_s, int* __restrict__ cand_r) {
+  const int64_t q = blockIdx.x;
+  const int j = blockIdx.y;
+  if (j < nprobe_of[q]) return;
+  const int64_t p = q * nprobe + j;
+  if (threadIdx.x == 0) {
+    pid[p] = -1;
+    ps[p] = -__builtin_inff();
+  }
+  for (int i = threadIdx.x; i < per_pair; i += 256) {
+    cand_s[p * per_pair + i] = -__builtin_inff();
+    cand_r[p * per_pair + i] = kEmptyRow;
+  }
+}
+
+void launch_absent_pairs(const int* nprobe_of, int64_t nq, int nprobe, int per_pair, int64_t* pid, float* ps,
+                         float* cs, int* cr, hipStream_t st) {
+  hipLaunchKernelGGL(absent_pairs_kernel, dim3((unsigned)nq, (unsigned)nprobe), dim3(256), 0, st, nprobe_of, nprobe,
+                     per_pair, pid, ps, cs, cr);
 }
 
 }  // namespace ivf

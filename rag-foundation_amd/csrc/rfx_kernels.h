@@ -209,8 +209,19 @@ int launch_build_lists(const int* labels, int64_t n, int m, const int8_t* codes,
                        hipStream_t st);
 int list_k(int k);
 // each query's nprobe best of m coarse scores (m <= 4096; else -1: use launch_topk_merge), in no order
-int launch_probe_select(const float* S, int64_t nq, int m, int nprobe, float* ps, int64_t* pid, hipStream_t st);
-int launch_group_pairs(const int64_t* probes, int P, int m, int* pair_off, int* pairs, hipStream_t st);
+// (nprobe_of: a count per question, nprobe the stride — DESIGN §4.16; the slots past a count: launch_absent_pairs)
+int launch_probe_select(const float* S, int64_t nq, int m, int nprobe, float* ps, int64_t* pid, hipStream_t st,
+                        const int* nprobe_of = nullptr);
+// skip: probes[p] < 0 marks a pair that does not exist
+int launch_group_pairs(const int64_t* probes, int P, int m, int* pair_off, int* pairs, hipStream_t st, bool skip = false);
+// pairs j >= nprobe_of[q]: probe id -1, their per_pair = splits * 4 * K candidate slots set empty
+void launch_absent_pairs(const int* nprobe_of, int64_t nq, int nprobe, int per_pair, int64_t* pid, float* ps, float* cs,
+                         int* cr, hipStream_t st);
+// a mask per question: masks = device table of row bitmaps, mask_of[q] = index or -1
+int launch_list_scan_multi(int K, int D, int m, int splits, const int8_t* codes, const float* inv, const int* ids,
+                           const int64_t* off, const int* pair_off, const int* pairs, int nprobe, const int8_t* qq,
+                           const float* qinv, float* cs, int* cr, const uint32_t* const* masks, const int* mask_of,
+                           hipStream_t st);
 int launch_list_scan(int K, int D, int m, int splits, const int8_t* codes, const float* inv, const int* ids, const int64_t* off,
                      const int* pair_off, const int* pairs, int nprobe, const int8_t* qq, const float* qinv,
                      float* cs, int* cr, const uint32_t* row_mask /* nullptr: every row eligible */, hipStream_t st);

@@ -149,6 +149,10 @@ SIGNATURES = {
     "rfx_ivf_search": ([_u64, _p, _i64, _i, _i, _i, _p, _p, _p, _sz, _p], _i),
     "rfx_ivf_search_masked": ([_u64, _p, _i64, _i, _i, _i, _p, _i64, _p, _p, _p, _sz, _p], _i),
     "rfx_ivf_search_rerank_masked": ([_u64, _p, _i64, _i, _i, _i, _i, _p, _i, _p, _i64, _p, _p, _p, _sz, _p], _i),
+    "rfx_ivf_search_multi": ([_u64, _p, _i64, _i, _i, _p, _i, _i64, _p, _p, _i, _p, _p, _p, _p, _p, _sz, _p], _i),
+    "rfx_ivf_search_rerank_multi": ([_u64, _p, _i64, _i, _i, _i, _p, _i, _p, _i, _i64, _p, _p, _i, _p, _p, _p, _p, _p, _sz,
+                                     _p],
+                                    _i),
     "rfx_search_masked": ([_u64, _p, _i64, _i, _p, _i64, _p, _p, _p, _sz, _p], _i),
     "rfx_search_records": ([_u64, _p, _i64, _i, _p, _i64, _i64, _p, _p, _sz, _p], _i),
     "rfx_search_segmented_workspace_bytes": ([_u64, _i64, _i, _i64, _psz], _i),

@@ -142,21 +142,62 @@ class IvfIndex:
             raise ValueError(f"row mask on {row_mask.device}, index on {self._dev()}")
         return ptr(row_mask), row_mask.numel()
 
+    def _multi(self, nq, nprobe, row_masks, mask_of, nprobes):
+        """The per-question form (rfx_ivf_search_multi): row_masks, a list of row bitmaps as
+        row_mask takes them; mask_of [nq], each question's index into it, -1 = no mask (default: 0 for every
+        question when the list holds one mask, -1 when it is empty); nprobes [nq], each question's probe count
+        (default: nprobe for all).  -> None when none of the three is given, else (table of the masks' device
+        pointers, n_masks, words, mask_of int32 [nq], nprobes int32 [nq], the largest probe count, and the host
+        copies of mask_of and nprobes, which the C ABI checks instead of reading the device arrays back)."""
+        if row_masks is None and mask_of is None and nprobes is None:
+            return None
+        masks = list(row_masks or [])
+        for m in masks:
+            self._mask(m)
+        if mask_of is None:
+            if len(masks) > 1:
+                raise ValueError("mask_of is needed with more than one row mask")
+            mask_of = [0 if masks else -1] * nq
+        if nprobes is None:
+            nprobes = [int(nprobe)] * nq
+        mo = torch.as_tensor(mask_of, dtype=torch.int32).reshape(-1).cpu().contiguous()
+        npr = torch.as_tensor(nprobes, dtype=torch.int32).reshape(-1).cpu().contiguous()
+        if mo.numel() != nq or npr.numel() != nq:
+            raise ValueError(f"mask_of and nprobes must hold one entry per question ({nq})")
+        nmax = int(npr.max()) if nq else max(int(nprobe or 1), 1)
+        table = torch.tensor([m.data_ptr() for m in masks] or [0], dtype=torch.int64)
+        words = min((m.numel() for m in masks), default=0)
+        # one host-to-device copy for the three arrays (the 8-byte pointers first)
+        nt = 2 * table.numel()
+        dev = torch.cat([table.view(torch.int32), mo, npr]).to(self._dev())
+        return dev[:nt].view(torch.int64), len(masks), words, dev[nt:nt + nq], dev[nt + nq:], nmax, mo, npr
+
     def search(self, queries: torch.Tensor, k: int, nprobe: int, workspace: torch.Tensor = None, stream=None,
-               row_mask: torch.Tensor = None):
+               row_mask: torch.Tensor = None, row_masks=None, mask_of=None, nprobes=None):
         """Top-k rows per query over the nprobe nearest lists: (scores f32 [nq][k], rows i64 [nq][k]).
         row_mask (optional): only rows whose bit is set rank (rfx_ivf_search_masked: the same probes, the
-        filter applied inside the list scan, before any top-k)."""
+        filter applied inside the list scan, before any top-k).  row_masks / mask_of / nprobes (exclusive with
+        row_mask): a mask and a probe count per question in one list search (_multi); question q's answer is
+        the one it gets alone at nprobes[q] under its own mask."""
         q, dt = self._rows(queries)
-        m, mw = self._mask(row_mask)
         nq = q.shape[0]
+        mu = self._multi(nq, nprobe, row_masks, mask_of, nprobes)
+        if mu is not None and row_mask is not None:
+            raise ValueError("row_mask and row_masks / mask_of / nprobes are exclusive")
+        if mu is not None:
+            nprobe = mu[5]
+        m, mw = self._mask(row_mask)
         out_s = torch.empty((nq, k), dtype=torch.float32, device=self._dev())
         out_r = torch.empty((nq, k), dtype=torch.int64, device=self._dev())
         need = self.workspace_bytes(nq, k, nprobe)
         ws = workspace if workspace is not None and workspace.numel() >= need else \
             torch.empty(max(need, 1), dtype=torch.uint8, device=self._dev())
         with torch.cuda.device(self.device):
-            if m is None:
+            if mu is not None:
+                check(lib.rfx_ivf_search_multi(self.handle, ptr(q), nq, dt, int(k), ptr(mu[0]), mu[1], mu[2], ptr(mu[3]),
+                                               ptr(mu[4]), mu[5], ptr(mu[6]), ptr(mu[7]), ptr(out_s), ptr(out_r),
+                                               ptr(ws), ws.numel(), stream_ptr(stream)))
+            elif m is None:
                 check(lib.rfx_ivf_search(self.handle, ptr(q), nq, dt, int(k), int(nprobe), ptr(out_s), ptr(out_r),
                                          ptr(ws), ws.numel(), stream_ptr(stream)))
             else:
@@ -165,11 +206,11 @@ class IvfIndex:
         return out_s, out_r
 
     def search_rerank(self, queries: torch.Tensor, k: int, nprobe: int, rows: torch.Tensor, rerank_k: int = None,
-                      stream=None, row_mask: torch.Tensor = None):
+                      stream=None, row_mask: torch.Tensor = None, row_masks=None, mask_of=None, nprobes=None):
         """IVF search keeping rerank_k candidates (default max(k, 16): lists of up to 16 keep the
         fast scan template), re-scored in f32 against the original rows [rows][dim] (insertion
-        order, e.g. DeviceIndex.read / the brute-force store).  row_mask: as search (the candidates
-        are then eligible rows only)."""
+        order, e.g. DeviceIndex.read / the brute-force store).  row_mask, or row_masks / mask_of / nprobes: as
+        search (the candidates are then eligible rows only)."""
         q, dt = self._rows(queries)
         if rows.dim() != 2 or rows.shape[1] != self.dim or rows.device != self._dev() or not rows.is_contiguous():
             raise ValueError(f"rows must be a contiguous [n][{self.dim}] tensor on {self._dev()}")
@@ -178,9 +219,14 @@ class IvfIndex:
         rdt = {v: k_ for k_, v in _lib.TORCH_DTYPES.items()}.get(rows.dtype)
         if rdt is None:
             raise ValueError("rows must be float32, bfloat16 or float16")
-        return self._rerank(q, dt, k, nprobe, ptr(rows), _lib.DTYPE_CODES[rdt], rerank_k, stream, row_mask)
+        return self._rerank(q, dt, k, nprobe, ptr(rows), _lib.DTYPE_CODES[rdt], rerank_k, stream, row_mask,
+                            self._multi(q.shape[0], nprobe, row_masks, mask_of, nprobes))
 
-    def _rerank(self, q, dt, k, nprobe, rows_p, rows_code, rerank_k, stream, row_mask=None):
+    def _rerank(self, q, dt, k, nprobe, rows_p, rows_code, rerank_k, stream, row_mask=None, mu=None):
+        if mu is not None and row_mask is not None:
+            raise ValueError("row_mask and row_masks / mask_of / nprobes are exclusive")
+        if mu is not None:
+            nprobe = mu[5]
         m, mw = self._mask(row_mask)
         rk = max(int(k), 16) if rerank_k is None else int(rerank_k)
         nq = q.shape[0]
@@ -190,7 +236,12 @@ class IvfIndex:
         check(lib.rfx_ivf_rerank_workspace_bytes(self.handle, nq, int(k), int(nprobe), rk, ctypes.byref(b)))
         ws = torch.empty(max(b.value, 1), dtype=torch.uint8, device=self._dev())
         with torch.cuda.device(self.device):
-            if m is None:
+            if mu is not None:
+                check(lib.rfx_ivf_search_rerank_multi(self.handle, ptr(q), nq, dt, int(k), rk, rows_p, rows_code,
+                                                      ptr(mu[0]), mu[1], mu[2], ptr(mu[3]), ptr(mu[4]), mu[5],
+                                                      ptr(mu[6]), ptr(mu[7]), ptr(out_s), ptr(out_r), ptr(ws),
+                                                      ws.numel(), stream_ptr(stream)))
+            elif m is None:
                 check(lib.rfx_ivf_search_rerank(self.handle, ptr(q), nq, dt, int(k), int(nprobe), rk, rows_p, rows_code,
                                                 ptr(out_s), ptr(out_r), ptr(ws), ws.numel(), stream_ptr(stream)))
             else:
@@ -201,18 +252,19 @@ class IvfIndex:
 
     # ---- serving from a store's DeviceIndex (rfx.store, config 5) ------------------------------------
     def search_index(self, queries: torch.Tensor, k: int, nprobe: int, index, rerank_k: int = None, stream=None,
-                     row_mask: torch.Tensor = None):
+                     row_mask: torch.Tensor = None, row_masks=None, mask_of=None, nprobes=None):
         """search_rerank against a DeviceIndex holding the same rows in the same order (row i of
         this index = row i of `index`).  Tombstoned rows are NaN there, so the exact re-rank drops
         them.  The caller holds the index owner's lock until the results are read (data_ptr).
-        row_mask: the index's own row mask (DeviceIndex.mask_tensor), as search."""
+        row_mask: the index's own row mask (DeviceIndex.mask_tensor), as search; row_masks / mask_of / nprobes:
+        a mask of the index and a probe count per question, as search."""
         q, dt = self._rows(queries)
         if index.dim != self.dim or index.device != self.device:
             raise ValueError("index dim / device differ from the IVF index")
         if index.rows < self.rows:
             raise ValueError(f"index holds {index.rows} rows, the IVF lists {self.rows}")
         return self._rerank(q, dt, k, nprobe, ctypes.c_void_p(index.data_ptr()), _lib.DTYPE_CODES[index.dtype],
-                            rerank_k, stream, row_mask)
+                            rerank_k, stream, row_mask, self._multi(q.shape[0], nprobe, row_masks, mask_of, nprobes))
 
     def train_from(self, index, row_ids, iters: int = 10) -> None:
         """k-means over the rows `row_ids` (sorted int64 numpy array) of a DeviceIndex."""

@@ -12,7 +12,7 @@ import torch
 from . import filters
 from .batcher import GroupBatcher
 from .embedder import DEFAULT_MAX_TOKENS, DEFAULT_OVERLAP, Embedder, featurize_texts
-from .store import ivf_filtered_mode, registry as default_registry
+from .store import ivf_filtered_mode, ivf_multi_mode, registry as default_registry
 from . import union as runion
 
 
@@ -244,6 +244,7 @@ class GpuRetriever:
         self.union = os.environ.get("RFX_UNION", "1") != "0"
         self.last_path = None  # "union" | "per-store" (tests, diagnostics)
         self.last_filter_path = None  # "segmented" | "masked" | "ivf": how the last filtered batch was searched
+        self.last_filter_list_searches = 0  # list searches the last filtered batch issued (IVF stores, §4.16)
         self.last_diversity = None  # "union" | "store" | None: where the last question was diversified
         self.last_hybrid = None  # "store" | None: the last question fused a dense and a lexical answer per store
 
@@ -411,7 +412,10 @@ class GpuRetriever:
         filters select too much of the store for that to pay (segmented_max_fraction), one masked search
         per distinct filter runs as before.  On an IVF store under RFX_IVF_FILTERED, a group of plain
         questions (no diversity) whose filter the store's rule sends to the posting lists is answered
-        there first (last_filter_path "ivf"); every other group goes through the choice above unchanged.
+        there first (last_filter_path "ivf") — two or more such groups in ONE list search at the batch's
+        largest k (LocalStore.search_lists_filtered_multi; a lone group, and every group under
+        RFX_IVF_MULTI=0, takes the one-mask search of §4.15, one per group;
+        last_filter_list_searches counts them); every other group goes through the choice above unchanged.
         Filtered diverse, hybrid and union-view questions keep the exact scan."""
         st = self.registry.get(name)
         if st is None:
@@ -430,15 +434,31 @@ class GpuRetriever:
             if ranges:
                 groups.append((filt, idxs, ranges))
         rest = groups
+        self.last_filter_list_searches = 0
         if self._lists_possible(st):  # plain groups the store's rule sends to its posting lists
             plain = [g for g in groups if all(len(items[i]) == 3 for i in g[1])]
             rest = [g for g in groups if not all(len(items[i]) == 3 for i in g[1])]
             if plain:
                 order = [i for _, idxs, _ in plain for i in idxs]
                 at = {i: p for p, i in enumerate(order)}
+                # one plain group is the one-mask search it always was (the per-question entry point costs a table
+                # upload and a launch more per call); two or more share ONE list search
+                multi = ivf_multi_mode() and len(plain) > 1
                 with torch.cuda.device(st.device):  # one embedding for all of them
                     q_all = self.embedder(st.dim).embed_texts([items[i][0] for i in order], st.dtype)
-                    for g in plain:
+                    if multi:  # ONE list search for every group the rule sends to the lists, at the batch's k
+                        kmax = max(items[i][1] for i in order)
+                        res = st.search_lists_filtered_multi(q_all, kmax, [items[i][2] for i in order])
+                        declined = set(range(len(order))) if res is None else set(res[2])
+                        rest += [g for g in plain if at[g[1][0]] in declined]
+                        if res is not None:
+                            self.last_filter_path = "ivf"
+                            self.last_filter_list_searches += 1
+                            s, r = res[0].tolist(), res[1].tolist()
+                            for i in order:
+                                if at[i] not in declined:
+                                    out[i] = (st, s[at[i]][:items[i][1]], r[at[i]][:items[i][1]])
+                    for g in ([] if multi else plain):
                         filt, idxs, _ = g
                         q = q_all[[at[i] for i in idxs]].contiguous()
                         res = st.search_lists_filtered(q, max(items[i][1] for i in idxs), filt)
@@ -446,6 +466,7 @@ class GpuRetriever:
                             rest.append(g)
                             continue
                         self.last_filter_path = "ivf"
+                        self.last_filter_list_searches += 1
                         s, r = res[0].tolist(), res[1].tolist()
                         for p, i in enumerate(idxs):
                             out[i] = (st, s[p][:items[i][1]], r[p][:items[i][1]])

@@ -463,9 +463,12 @@ class ShardedIvf:
                 p.add_from(sh, sh.rows)
 
     def search_index(self, queries: torch.Tensor, k: int, nprobe: int, index=None, rerank_k: int = None, stream=None,
-                     row_mask=None):
+                     row_mask=None, row_masks=None, mask_of=None, nprobes=None):
         """row_mask: the per-shard list of masks ShardedIndex.search takes (mask_tensor); shard i's goes to
-        shard i's list scan, nothing else changes, so a filtered answer is the one-device answer too."""
+        shard i's list scan, nothing else changes, so a filtered answer is the one-device answer too.
+        row_masks / mask_of / nprobes (IvfIndex.search): row_masks is a list of such per-shard
+        lists, one per filter; shard i's scan gets the table [m[i] for m in row_masks], every shard the same
+        mask_of and nprobes."""
         from .ivf import rerank_candidates
         sidx = self.sidx
         rk = max(int(k), 16) if rerank_k is None else int(rerank_k)
@@ -480,7 +483,9 @@ class ShardedIvf:
                 st.wait_stream(src)
                 with torch.cuda.device(d), torch.cuda.stream(st):
                     q = queries.to(torch.device("cuda", d), non_blocking=True)
-                    s, r = p.search(q, rk, nprobe, stream=st, row_mask=row_mask[i] if row_mask is not None else None)
+                    s, r = p.search(q, rk, nprobe, stream=st, row_mask=row_mask[i] if row_mask is not None else None,
+                                    row_masks=[m[i] for m in row_masks] if row_masks is not None else None,
+                                    mask_of=mask_of, nprobes=nprobes)
                     recs.append(topk_merge_records(s, r, rk, row_offset=base, stream=st))
                 qs.append(q)
             cands = self._merge_each(sidx._exchange(recs, nq, rk, everywhere=True), rk)

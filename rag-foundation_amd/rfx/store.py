@@ -138,6 +138,13 @@ def ivf_filtered_mode() -> str:
     return m if m in ("auto", "1") else "0"
 
 
+def ivf_multi_mode() -> bool:
+    """RFX_IVF_MULTI: 1 (default) = a batch of filtered questions under different filters takes the posting
+    lists in ONE list search (LocalStore.search_lists_filtered_multi); 0 = one list search per
+    filter group, as before.  Read at every batch."""
+    return os.environ.get("RFX_IVF_MULTI", "1").strip() != "0"
+
+
 def ivf_filter_nprobe(nprobe, nlist, selected, live, mode):
     """Probe count of a filtered IVF search, or None for the exact path.  A filter that keeps
     `selected` of the `live` rows leaves a fixed nprobe scanning selected / live of the eligible rows an
@@ -924,6 +931,47 @@ class LocalStore:
             s, r = self.ivf.search_index(queries, k, nprobe, self.index, rerank_k=min(64, max(16, 2 * int(k))),
                                          row_mask=self.row_mask(metadata_filter))
             return s.cpu(), r.cpu()
+
+    def search_lists_filtered_multi(self, queries, k, filters_):
+        """One list search for questions under different filters.  filters_: one metadata filter
+        per question; equal filters share a mask.  The rule (filtered_nprobe) is evaluated once per distinct
+        filter and, with the masks and the search, is one evaluation under self.lock.  The questions whose
+        filter the rule sends to the lists are answered together — each at its own filter's probe count under
+        its own mask, re-ranked at the depth for k as search_lists_filtered does — in one call of
+        search_index.  -> (scores [nq][k], rows [nq][k], declined): host tensors, and the indices of the
+        questions the rule keeps exact (their lines are padding, (-inf, -1)); None when nothing takes the
+        lists (mode 0, a flat store, every filter declined)."""
+        import torch
+        nq = len(filters_)
+        if queries.shape[0] != nq:
+            raise ValueError(f"{queries.shape[0]} questions, {nq} filters")
+        if ivf_filtered_mode() == "0" or self.ivf is None:
+            return None
+        with self.lock:
+            table, mask_of, nprobes, slot = [], [-1] * nq, [0] * nq, {}
+            for filt, idxs in filters.group_by_filter(list(filters_)):
+                nprobe = self.filtered_nprobe(filt)
+                mask = self.row_mask(filt) if nprobe is not None else None
+                if mask is None:
+                    continue
+                key = id(mask)
+                if key not in slot:
+                    slot[key] = len(table)
+                    table.append(mask)
+                for i in idxs:
+                    mask_of[i], nprobes[i] = slot[key], nprobe
+            take = [i for i in range(nq) if nprobes[i]]  # in filter-group order: a staged batch of the list scan
+            take.sort(key=lambda i: mask_of[i])          # then mostly holds one mask (k_ivf.hip list_scan_multi_kernel)
+            if not take:
+                return None
+            out_s = torch.full((nq, k), float("-inf"), dtype=torch.float32)
+            out_r = torch.full((nq, k), -1, dtype=torch.int64)
+            q = queries if len(take) == nq and take == list(range(nq)) else queries[take]
+            s, r = self.ivf.search_index(q, k, max(nprobes), self.index, rerank_k=min(64, max(16, 2 * int(k))),
+                                         row_masks=table, mask_of=[mask_of[i] for i in take],
+                                         nprobes=[nprobes[i] for i in take])
+            out_s[take], out_r[take] = s.cpu(), r.cpu()
+            return out_s, out_r, [i for i in range(nq) if not nprobes[i]]
 
     def search_filtered(self, queries, k, metadata_filter):
         """(scores, rows, path) of the top-k rows per query among the rows the filter selects, scores and rows
