@@ -233,6 +233,32 @@ int rfx_mmr_select(rfx_index_t h, const void* queries_d, int64_t nq, int n_cand_
                    const float* cand_scores_d, const int64_t* cand_rows_d, /* [nq][n_cand_max] */
                    float* out_scores_d, int64_t* out_rows_d, float* out_obj_d /* may be NULL */,
                    void* ws_d, size_t ws_bytes, void* stream);
+/* Distinct-document search: the collapse of a sorted candidate list by document, one launch for
+ * the batch.  The retrieval slice of ask_stream (gemini_rag.py:517-551): the reference's file-search tool answers
+ * with documents, while every rfx_search* ranks rows, and a row is a chunk, so one long file fills all k places
+ * with its own chunk windows.  The rule of the whole search: take the full ranking of the live rows the filter
+ * selects (fl32 of the f64 dot; score desc, row asc); keep a row when no earlier row of the ranking belongs to the
+ * same document; the answer is the first k kept rows in that order, then (-inf, -1).  So a document's hit is its
+ * best chunk, equal scores go to the lower row, and fewer than k live documents answer with padding.
+ * This call is one round of it.  Input per query: cand_scores_d / cand_rows_d [nq][n_cand], the answer of any
+ * rfx_search* at k = n_cand on this index (sorted, padded at the end); row_doc_d [n_row_doc] = the document
+ * ordinal of every row, -1 for a row of no live document; have_d [nq] (NULL = zeros) = how many picks
+ * out_*[q] already holds from earlier rounds.  A candidate with a row outside [0, rows) is padding.  A candidate
+ * is dropped when its document is < 0, when an earlier candidate holds the same document, or when the document
+ * is among out_docs_d[q][0 .. have_d[q]).  The others are appended in list order: slots have_d[q] .. k - 1 of
+ * out_scores_d / out_rows_d / out_docs_d [nq][k] receive them, then (-inf, -1, -1); slots below have_d[q] are
+ * not touched.  out_n_d[q] = the new count (have_d may be out_n_d of the round before); out_done_d[q] = 1 when
+ * the count reached k, or when the list held fewer than n_cand valid entries (the search ran out of rows).
+ * When the candidates of a later round are the answer of a search over the selected rows WITHOUT the rows of
+ * the documents already found, every one of them ranks after every row seen before, so appending keeps the
+ * order of the rule (rfx.index.DeviceIndex.search_distinct runs the rounds).
+ * No workspace; stream-ordered after the search that wrote the candidates.  RFX_EINVAL before anything is
+ * enqueued: k or n_cand outside 1..64, nq outside 1..1024, n_row_doc below the index's rows, a pointer other
+ * than have_d NULL.  Any handle rfx_mmr_select accepts. */
+int rfx_distinct_collapse(rfx_index_t h, const int32_t* row_doc_d, int64_t n_row_doc, int64_t nq, int n_cand, int k,
+                          const float* cand_scores_d, const int64_t* cand_rows_d, const int32_t* have_d /* may be NULL */,
+                          float* out_scores_d, int64_t* out_rows_d, int32_t* out_docs_d, int32_t* out_n_d,
+                          int32_t* out_done_d, void* stream);
 /* Merge per-query candidate lists into the final top-k.  rows are int32 (rows_are_i64 = 0) or
  * int64 (1); row_offset is added to every returned row (shard base for multi-GPU). */
 int rfx_topk_merge(const float* cand_scores_d, const void* cand_rows_d, int rows_are_i64,

@@ -35,6 +35,7 @@
 
 #include "k_compact.h"
 #include "k_mmr.h"
+#include "k_distinct.h"
 #include "rfx_kernels.h"
 
 namespace {
@@ -2612,6 +2613,33 @@ int rfx_mmr_select(rfx_index_t h, const void* queries_d, int64_t nq, int n_cand_
                              (const int*)(ws + L.ncand_off), cand_scores_d, cand_rows_d, out_scores_d, out_rows_d,
                              out_obj_d, st) != 0)
     return fail(RFX_EUNSUPPORTED, "mmr select launch rejected");
+  RFX_HIP(hipGetLastError());
+  return RFX_OK;
+}
+
+// ---- distinct-document search: collapse a sorted candidate list by document (k_distinct.h) ----
+int rfx_distinct_collapse(rfx_index_t h, const int32_t* row_doc_d, int64_t n_row_doc, int64_t nq, int n_cand, int k,
+                          const float* cand_scores_d, const int64_t* cand_rows_d, const int32_t* have_d,
+                          float* out_scores_d, int64_t* out_rows_d, int32_t* out_docs_d, int32_t* out_n_d,
+                          int32_t* out_done_d, void* stream) {
+  auto ix = get(h);
+  if (!ix) return fail(RFX_EINVAL, "unknown index handle");
+  RFX_RLOCK(ix);  // the row count moves with every append
+  if (n_cand < 1 || n_cand > rfx::kDistinctMaxCand)
+    return fail(RFX_EINVAL, "n_cand=%d out of range [1, %d]", n_cand, rfx::kDistinctMaxCand);
+  if (k < 1 || k > rfx::kDistinctMaxCand) return fail(RFX_EINVAL, "k=%d out of range [1, %d]", k, rfx::kDistinctMaxCand);
+  if (nq < 1 || nq > rfx::kDistinctMaxNq)
+    return fail(RFX_EINVAL, "nq=%lld out of [1, %d]", (long long)nq, rfx::kDistinctMaxNq);
+  if (n_row_doc < ix->rows)
+    return fail(RFX_EINVAL, "row_doc holds %lld entries, the index %lld rows", (long long)n_row_doc, (long long)ix->rows);
+  if (!row_doc_d || !cand_scores_d || !cand_rows_d || !out_scores_d || !out_rows_d || !out_docs_d || !out_n_d ||
+      !out_done_d)
+    return fail(RFX_EINVAL, "null row_doc / candidates / outputs");
+  RFX_HIP(hipSetDevice(ix->device));
+  if (rfx::launch_distinct_collapse(row_doc_d, ix->rows, (int)nq, n_cand, k, cand_scores_d, cand_rows_d, have_d,
+                                    out_scores_d, out_rows_d, out_docs_d, out_n_d, out_done_d,
+                                    (hipStream_t)stream) != 0)
+    return fail(RFX_EUNSUPPORTED, "distinct collapse launch rejected");
   RFX_HIP(hipGetLastError());
   return RFX_OK;
 }

@@ -160,6 +160,7 @@ SIGNATURES = {
     "rfx_segmented_plan": ([_i64, _i, _i, _i64, _i, _i, _p, _p, _p, _p, _i64, _pi64, _pi], _i),
     "rfx_mmr_workspace_bytes": ([_u64, _i64, _i, _psz], _i),
     "rfx_mmr_select": ([_u64, _p, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p], _i),
+    "rfx_distinct_collapse": ([_u64, _p, _i64, _i64, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p], _i),
     "rfx_search_plan": ([_u64, _i64, _i, _pi], _i),
     "rfx_rescore_topk": ([_u64, _p, _i64, _i, _i64, _p, _p, _p, _p], _i),
     "rfx_sharded_search": ([_i, _p, _p, _p, _p, _i64, _i, _p, _p, _p, _p, _p, _p, _u64, _p, _p, _p, _p], _i),

@@ -29,6 +29,7 @@ from dataclasses import dataclass
 from types import SimpleNamespace
 from typing import Any, List, Optional, Sequence
 
+from .distinct import env_default as env_default_distinct
 from .metrics import observe
 
 logger = logging.getLogger(__name__)
@@ -104,6 +105,9 @@ class LocalGpuRag:
         # alpha of every question (1 = dense only, 0 = keywords only); unset = off
         alpha = os.environ.get("RFX_HYBRID_ALPHA", "").strip()
         self.hybrid = float(alpha) if alpha else None
+        # distinct-document search (top-k documents, one best chunk each): RFX_DISTINCT=1 makes it
+        # the default of every question; unset or 0 = off (the k best chunks, whatever files they come from)
+        self.distinct = env_default_distinct()
         self.is_mock = True
 
     # -------- Stores --------
@@ -155,17 +159,24 @@ class LocalGpuRag:
     # -------- Query (sync & stream) --------
     def retrieve(self, question: str, store_names: Sequence[str], k: Optional[int] = None,
                  metadata_filter: Optional[Any] = None, diversity: Optional[Any] = None,
-                 hybrid: Optional[Any] = None):
+                 hybrid: Optional[Any] = None, distinct: Optional[Any] = None):
         """Top-k hits.  k: the request's top_k (the reference route drops it,
         chat.py:66), default self.top_k; 1..64.  diversity: a lambda in [0, 1] or {"lambda": ..,
         "fetch_k": ..} picks the k hits by MMR from the fetch_k best (GpuRetriever.search); None = the
         default of RFX_MMR_LAMBDA (unset: off).  hybrid: an alpha in [0, 1] or {"alpha", "fetch_k", "rrf_c",
         "k1", "b"} fuses the dense answer with the BM25 answer over the chunk texts (GpuRetriever.search;
         ValueError on a sharded or IVF store and together with diversity); None = the default of
-        RFX_HYBRID_ALPHA (unset: off)."""
+        RFX_HYBRID_ALPHA (unset: off).  distinct: True or {"fetch_k": n} returns the best chunks of k DIFFERENT
+        files (GpuRetriever.search; ValueError on a sharded or IVF store and together with diversity or hybrid);
+        False = off; None = the default of RFX_DISTINCT (unset: off)."""
         filt = metadata_filter if self.apply_filters else None
         div = self.diversity if diversity is None else diversity
         hyb = self.hybrid if hybrid is None else hybrid
+        dst = self.distinct if distinct is None else distinct
+        if dst:
+            kw = {name: v for name, v in (("diversity", div), ("hybrid", hyb)) if v is not None}
+            return self.retriever.search(list(store_names or []), question, self.top_k if k is None else int(k),
+                                         metadata_filter=filt, distinct=dst, **kw)
         if hyb is not None:
             kw = {} if div is None else {"diversity": div}
             return self.retriever.search(list(store_names or []), question, self.top_k if k is None else int(k),
@@ -178,20 +189,21 @@ class LocalGpuRag:
 
     def ask(self, *, contents: Any, store_names: Sequence[str], metadata_filter: Optional[Any], model: str,
             system: Optional[str] = None, top_k: Optional[int] = None, diversity: Optional[Any] = None,
-            hybrid: Optional[Any] = None) -> Any:
+            hybrid: Optional[Any] = None, distinct: Optional[Any] = None) -> Any:
         with observe("generate"):
-            hits = self.retrieve(contents_to_text(contents), store_names, top_k, metadata_filter, diversity, hybrid)
+            hits = self.retrieve(contents_to_text(contents), store_names, top_k, metadata_filter, diversity, hybrid,
+                                 distinct)
             return build_response(hits, store_names)
 
     def ask_stream(self, *, contents: Any, store_names: Sequence[str], metadata_filter: Optional[Any], model: str,
                    system: Optional[str] = None, top_k: Optional[int] = None, diversity: Optional[Any] = None,
-                   hybrid: Optional[Any] = None):
+                   hybrid: Optional[Any] = None, distinct: Optional[Any] = None):
         """The reference's keyword set plus an optional top_k (callers that do not pass it get
         self.top_k, so the reference call site chat.py:499-505 works unchanged)."""
         with observe("generate_stream"):
             text = contents_to_text(contents)
-            resp = build_response(self.retrieve(text, store_names, top_k, metadata_filter, diversity, hybrid),
-                                  store_names)
+            resp = build_response(self.retrieve(text, store_names, top_k, metadata_filter, diversity, hybrid,
+                                                distinct), store_names)
         yield SimpleNamespace(text=f"[mock-mode] {text or 'response'}", candidates=None,
                               usage_metadata=SimpleNamespace(prompt_token_count=0, candidates_token_count=0))
         yield resp

@@ -102,6 +102,45 @@ def group_by_filter(metadata_filters) -> list:
     return list(groups.values())
 
 
+def _check_ranges(ranges, what: str) -> list:
+    out, end = [], 0
+    for first, count in ranges:
+        first, count = int(first), int(count)
+        if first < 0 or count < 0:
+            raise ValueError(f"{what}: range ({first}, {count}) is negative")
+        if count == 0:
+            continue
+        if first < end:
+            raise ValueError(f"{what}: range ({first}, {count}) starts before {end} (ranges must ascend and not overlap)")
+        out.append((first, count))
+        end = first + count
+    return out
+
+
+def subtract_ranges(ranges, minus) -> list:
+    """`ranges` without the rows of `minus`: both lists of (first, count) row ranges, ascending and disjoint
+    (empty ranges are skipped); the result has the same form, touching pieces kept apart as they came.
+    ValueError for a list that does not ascend or overlaps itself.  Pure host code: the remainder a
+    distinct-document question still has to search once the rows of the documents it found are taken out
+    (DeviceIndex.search_distinct)."""
+    ranges, minus = _check_ranges(ranges, "ranges"), _check_ranges(minus, "minus")
+    out, j = [], 0
+    for first, count in ranges:
+        at, end = first, first + count
+        while j < len(minus) and minus[j][0] + minus[j][1] <= at:
+            j += 1
+        i = j
+        while i < len(minus) and minus[i][0] < end:
+            m0, m1 = minus[i][0], minus[i][0] + minus[i][1]
+            if m0 > at:
+                out.append((at, m0 - at))
+            at = max(at, m1)
+            i += 1
+        if at < end:
+            out.append((at, end - at))
+    return out
+
+
 def row_mask_words(n_rows: int, ranges: Iterable[Tuple[int, int]]) -> np.ndarray:
     """Bitmap of (first, count) row ranges: int32 words, bit (r & 31) of word r >> 5 = row r
     (the layout rfx_search_masked reads), (n_rows + 31) // 32 words (at least one)."""

@@ -287,6 +287,112 @@ class DeviceIndex:
         s, r = self.search(queries, int(fetch_k), row_mask=row_mask)
         return self.mmr_select(queries, s, r, int(k), lam=lam)
 
+    # ---- distinct-document search (top-k documents, one best chunk each) --------------------
+    def distinct_collapse(self, scores: torch.Tensor, rows: torch.Tensor, k: int, row_doc: torch.Tensor,
+                          have: torch.Tensor = None, out=None, stream=None):
+        """One collapse of sorted candidate lists by document (rfx_distinct_collapse).  scores f32 / rows int64
+        [nq][n_cand] as a search at k = n_cand returns them; row_doc int32 [>= rows] = every row's document
+        ordinal, -1 for a row of no live document.  out: None (fresh tensors), or the (scores f32 [nq][k],
+        rows int64 [nq][k], docs int32 [nq][k], n int32 [nq], done int32 [nq]) of the round before, which
+        with have (int32 [nq], usually out's n) are appended to.  Returns that 5-tuple."""
+        if scores.shape != rows.shape or scores.dim() != 2:
+            raise ValueError("candidates must be [nq][n_cand] scores and rows of equal shape")
+        dev = scores.device
+        if scores.dtype != torch.float32 or rows.dtype != torch.int64 or not scores.is_cuda or rows.device != dev:
+            raise ValueError("candidates must be (float32, int64) tensors on one device")
+        if row_doc.dtype != torch.int32 or row_doc.dim() != 1 or row_doc.device != dev or not row_doc.is_contiguous():
+            raise ValueError("row_doc must be a contiguous 1-D int32 tensor on the candidates' device")
+        cs, cr = scores.contiguous(), rows.contiguous()
+        nq, n_cand = cs.shape
+        if out is None:
+            out = (torch.empty((nq, k), dtype=torch.float32, device=dev),
+                   torch.empty((nq, k), dtype=torch.int64, device=dev),
+                   torch.empty((nq, k), dtype=torch.int32, device=dev),
+                   torch.empty((nq,), dtype=torch.int32, device=dev),
+                   torch.empty((nq,), dtype=torch.int32, device=dev))
+        else:
+            shapes = ((nq, k), (nq, k), (nq, k), (nq,), (nq,))
+            dtypes = (torch.float32, torch.int64, torch.int32, torch.int32, torch.int32)
+            if len(out) != 5 or any(t.shape != s or t.dtype != d or t.device != dev or not t.is_contiguous()
+                                    for t, s, d in zip(out, shapes, dtypes)):
+                raise ValueError(f"out must be contiguous (f32, i64, i32 [{nq}][{k}]; i32, i32 [{nq}]) tensors")
+        if have is not None and (have.dtype != torch.int32 or have.shape != (nq,) or have.device != dev
+                                 or not have.is_contiguous()):
+            raise ValueError(f"have must be a contiguous int32 [{nq}] tensor on the candidates' device")
+        with torch.cuda.device(dev):
+            check(lib.rfx_distinct_collapse(self.handle, ptr(row_doc), row_doc.numel(), nq, int(n_cand), int(k),
+                                            ptr(cs), ptr(cr), ptr(have) if have is not None else None,
+                                            ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(out[3]), ptr(out[4]),
+                                            stream_ptr(stream)))
+        return out
+
+    def search_distinct(self, queries: torch.Tensor, k: int, row_doc: torch.Tensor, doc_ranges, fetch_k: int = None,
+                        row_mask: torch.Tensor = None, select_ranges=None):
+        """The exact top-k DOCUMENTS with one best chunk each (rfx.distinct states the rule): the search at
+        fetch_k (default default_fetch_k(k); whichever plan `search` takes) and the collapse, then completion
+        rounds — ONE segmented search at k = 64 over, per open question, the selected rows without the rows
+        of the documents it has found, and a collapse that appends (rfx.distinct.run_rounds).
+        row_doc int32 [rows] on the device and doc_ranges [n_docs][2] (first row, rows) describe the documents
+        (LocalStore.row_docs); row_mask and select_ranges are the same filter as a bitmap (round 1) and as
+        ascending disjoint (first, count) ranges (the completion).  An index whose shape the segmented search
+        refuses takes one masked search per open question instead.  Returns (scores f32 [nq][k], rows int64
+        [nq][k], docs int32 [nq][k], rounds): device tensors, padded (-inf, -1, -1)."""
+        from . import distinct, filters
+        k = int(k)
+        fetch_k = distinct.default_fetch_k(k) if fetch_k is None else int(fetch_k)
+        if not 1 <= k <= fetch_k <= 64:
+            raise ValueError(f"need 1 <= k <= fetch_k <= 64, got k={k} fetch_k={fetch_k}")
+        q = self._check_queries(queries)
+        nq, dev = q.shape[0], q.device
+        if not 1 <= nq <= 1024:
+            raise ValueError(f"nq={nq} out of [1, 1024]")
+        n_rows = self.rows
+        if row_doc.numel() == 0:  # an empty index: every candidate is padding, the table is never read
+            row_doc = torch.full((1,), -1, dtype=torch.int32, device=dev)
+        index = self
+
+        class Ops:
+            out = None
+
+            def first(self):
+                return index.search(q, fetch_k, row_mask=row_mask)
+
+            def collapse(self, cand, have):
+                self.out = index.distinct_collapse(cand[0], cand[1], k, row_doc, self.out[3] if have else None,
+                                                   self.out if have else None)
+
+            def read(self):  # one copy to the host: n, done and the docs in one int32 tensor
+                host = torch.cat([self.out[3], self.out[4], self.out[2].reshape(-1)]).cpu().numpy()
+                return host[:nq], host[nq:2 * nq], host[2 * nq:].reshape(nq, k)
+
+            def _scatter(self, open_q, s, r):
+                cs = torch.full((nq, distinct.COMPLETION_K), float("-inf"), dtype=torch.float32, device=dev)
+                cr = torch.full((nq, distinct.COMPLETION_K), -1, dtype=torch.int64, device=dev)
+                at = torch.as_tensor(open_q, dtype=torch.int64, device=dev)
+                cs[at], cr[at] = s, r
+                return cs, cr
+
+            def segmented(self, open_q, ranges):
+                at = torch.as_tensor(open_q, dtype=torch.int64, device=dev)
+                try:
+                    s, r = index.search_segmented(q.index_select(0, at), distinct.COMPLETION_K,
+                                                  [([i], rg) for i, rg in enumerate(ranges)])
+                except _lib.RfxError as e:
+                    if e.code == _lib.RFX_EUNSUPPORTED:
+                        raise distinct.SegmentedUnsupported(str(e))
+                    raise
+                return self._scatter(open_q, s, r)
+
+            def masked(self, open_q, ranges):
+                res = [index.search(q[i:i + 1], distinct.COMPLETION_K,
+                                    row_mask=index.mask_tensor(filters.row_mask_words(n_rows, rg)))
+                       for i, rg in zip(open_q, ranges)]
+                return self._scatter(open_q, torch.cat([s for s, _ in res]), torch.cat([r for _, r in res]))
+
+        ops = Ops()
+        rounds = distinct.run_rounds(ops, nq, k, n_rows, doc_ranges, select_ranges)
+        return ops.out[0], ops.out[1], ops.out[2], rounds
+
     def search_records(self, queries: torch.Tensor, k: int, row_offset: int = 0, out: torch.Tensor = None,
                        workspace: torch.Tensor = None, stream=None, row_mask: torch.Tensor = None) -> torch.Tensor:
         """The search as [nq][k][2] int64 merge records (score bits, row + row_offset): one shard's

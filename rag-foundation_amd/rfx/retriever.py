@@ -11,6 +11,7 @@ import torch
 
 from . import filters
 from .batcher import GroupBatcher
+from .distinct import DISTINCT_ERROR, parse_distinct
 from .embedder import DEFAULT_MAX_TOKENS, DEFAULT_OVERLAP, Embedder, featurize_texts
 from .store import ivf_filtered_mode, ivf_multi_mode, registry as default_registry
 from . import union as runion
@@ -144,6 +145,16 @@ def parse_hybrid(hybrid, k: int):
     return alpha, fetch_k, rrf_c, k1, b
 
 
+_DISTINCT = "\x00distinct"  # tag of a store's distinct-document batchers (no filter_key starts with NUL)
+
+
+def _distinct_ok(st) -> bool:
+    """A flat store on one device whose index runs the distinct-document search (DeviceIndex.search_distinct)
+    and which knows its rows' documents (LocalStore.row_docs)."""
+    return hasattr(st.index, "search_distinct") and hasattr(st, "row_docs") and \
+        getattr(st, "spec", {}).get("kind", "flat") == "flat"
+
+
 def _diversity_ok(st) -> bool:
     """A flat store on one device: its index selects on the device (DeviceIndex.mmr_select) and no IVF
     lists answer in its place."""
@@ -247,6 +258,7 @@ class GpuRetriever:
         self.last_filter_list_searches = 0  # list searches the last filtered batch issued (IVF stores, §4.16)
         self.last_diversity = None  # "union" | "store" | None: where the last question was diversified
         self.last_hybrid = None  # "store" | None: the last question fused a dense and a lexical answer per store
+        self.last_distinct_rounds = None  # rounds of the last distinct-document batch (1 = the first search sufficed)
 
     @property
     def registry(self):
@@ -405,6 +417,57 @@ class GpuRetriever:
                 _BATCHERS[key] = b
             return b
 
+    def _run_distinct_batch(self, name, metadata_filter, items):
+        """Batch runner of a store's distinct-document questions, items (question, k, fetch_k): one embedding,
+        then DeviceIndex.search_distinct at the largest k and the largest fetch_k (the answer is exact at any
+        fetch_k, and the first k of the rule's answer at a larger k is its answer at k); each item takes its
+        first k.  A filter applies as the row mask of round 1 and as the select ranges of the completion.  The
+        whole batch runs under the store's lock and one row numbering: no append, delete or compaction moves
+        the rows or their documents between the rounds."""
+        st = self.registry.get(name)
+        if st is None:
+            return [None] * len(items)
+        if not _distinct_ok(st):
+            raise ValueError(DISTINCT_ERROR)
+        kmax = max(it[1] for it in items)
+        fetch = max(it[2] for it in items)
+        rounds = [None]
+
+        def run():
+            with torch.cuda.device(st.device), st.lock:
+                mask = st.row_mask(metadata_filter) if metadata_filter is not None else None
+                if metadata_filter is not None and mask is None:
+                    return None
+                sel = st.segment_ranges(metadata_filter) if metadata_filter is not None else None
+                row_doc, doc_ranges, _ = st.row_docs()
+                q = self.embedder(st.dim).embed_texts([it[0] for it in items], st.dtype)
+                s, r, _, rounds[0] = st.index.search_distinct(q, kmax, row_doc, doc_ranges, fetch_k=fetch,
+                                                              row_mask=mask, select_ranges=sel)
+                s, r = s.cpu().tolist(), r.cpu().tolist()
+            return [(s[i][:it[1]], r[i][:it[1]]) for i, it in enumerate(items)]
+
+        res, gen = _numbered(st, run)
+        if res is None:
+            return [None] * len(items)
+        self.last_distinct_rounds = rounds[0]
+        return [_answer(st, s, r, gen) for s, r in res]
+
+    def _distinct_batcher(self, name, metadata_filter):
+        # distinct questions of a store ride batchers of their own, keyed like the hybrid ones (store, a distinct
+        # tag, the filter's key): no existing batch ever changes shape
+        key = (name, f"{_DISTINCT}:{filters.filter_key(metadata_filter)}", id(self.registry))
+        with _STATE_LOCK:
+            b = _BATCHERS.get(key)
+            if b is None:
+                if self.registry.on_evict.count(_purge_batchers) == 0:
+                    self.registry.on_evict.append(_purge_batchers)
+                b = GroupBatcher(lambda items, n=name, f=metadata_filter: self._run_distinct_batch(n, f, items),
+                                 max_batch=256)
+                if len(_BATCHERS) >= 4096:
+                    _BATCHERS.clear()
+                _BATCHERS[key] = b
+            return b
+
     def _run_filtered_batch(self, name, items):
         """Batch runner of a store's filtered questions, items (question, k, filter): the items are grouped
         by filter and each group's row ranges resolved (a filter that matches no file answers None); then
@@ -537,11 +600,19 @@ class GpuRetriever:
         st = self.registry.get(name)
         return st is not None and hasattr(st.index, "search_segmented") and hasattr(st, "segment_ranges")
 
-    def search_store(self, name, question, k, metadata_filter=None, diversity=None, hybrid=None):
+    def search_store(self, name, question, k, metadata_filter=None, diversity=None, hybrid=None, distinct=None):
         """(store, scores, rows) of one question against one store, or None when the store is
         gone or the filter selects no row of it; batched with concurrent callers of the same
         store (filtered questions of a store share one batch, whatever their filters).
-        hybrid: parse_hybrid's tuple; the scores are then the fused ones (masked path under a filter)."""
+        hybrid: parse_hybrid's tuple; the scores are then the fused ones (masked path under a filter).
+        distinct: parse_distinct's fetch_k; the rows are then the best chunks of k different files."""
+        if distinct is not None:
+            if diversity or hybrid is not None:
+                raise ValueError(DISTINCT_ERROR)
+            item = (question, int(k), int(distinct))
+            if self.batching:
+                return self._distinct_batcher(name, metadata_filter).submit(item)
+            return self._run_distinct_batch(name, metadata_filter, [item])[0]
         if hybrid is not None:
             if diversity:
                 raise ValueError(HYBRID_ERROR)
@@ -682,7 +753,7 @@ class GpuRetriever:
             return b.submit((question, int(k)) + ((diversity,) if diversity else ()))
         return self._run_union_batch(tuple(names), filt, [(question, int(k)) + ((diversity,) if diversity else ())])[0]
 
-    def search(self, store_names, question, k, metadata_filter=None, diversity=None, hybrid=None):
+    def search(self, store_names, question, k, metadata_filter=None, diversity=None, hybrid=None, distinct=None):
         """Top-k hits over the union of the named stores, rank order (score desc, store order,
         row asc).  metadata_filter: {key: scalar | [scalars]} over upload metadata (rfx.filters).
         Several flat stores on one device: one scan of their union (rfx.union).
@@ -693,7 +764,12 @@ class GpuRetriever:
         hybrid: None, an alpha in [0, 1], or {"alpha", "fetch_k", "rrf_c", "k1", "b"} (parse_hybrid): each store
         answers with the reciprocal-rank fusion of its dense and its BM25 top fetch_k (alpha 1 = dense only),
         Hit.score is the fused score, and several stores are merged by it (never a union view).  ValueError
-        (HYBRID_ERROR) on a sharded or IVF store and together with diversity."""
+        (HYBRID_ERROR) on a sharded or IVF store and together with diversity.
+        distinct: None, True or {"fetch_k": n} (parse_distinct): the k hits are the best chunks of k DIFFERENT
+        files — of the full ranking, a row is kept when no earlier row belongs to the same file (DESIGN §4.17;
+        exact over the whole store, not a post-filter of the best rows).  Several stores answer each on its own
+        and are merged by score (files of different stores are different documents), never a union view.
+        ValueError (DISTINCT_ERROR) on a sharded or IVF store and together with diversity or hybrid."""
         k = int(k)
         if not 1 <= k <= 64:
             raise ValueError(f"top_k={k} out of range [1, 64]")
@@ -702,10 +778,13 @@ class GpuRetriever:
         hyb = parse_hybrid(hybrid, k)
         if hyb and div:  # an RRF score is not a similarity: the MMR objective would be meaningless
             raise ValueError(HYBRID_ERROR)
+        dst = parse_distinct(distinct, k)
+        if dst and (div or hyb):
+            raise ValueError(DISTINCT_ERROR)
         self.last_diversity = None
         self.last_hybrid = None
         names = list(dict.fromkeys(store_names or []))
-        if self.union and len(names) > 1 and not hyb:
+        if self.union and len(names) > 1 and not hyb and not dst:
             res = self._search_union(names, question, k, filt, div)
             if res is not None:
                 self.last_path = "union"
@@ -728,7 +807,10 @@ class GpuRetriever:
                 raise ValueError(DIVERSITY_ERROR)
             if hyb and not _diversity_ok(st):
                 raise ValueError(HYBRID_ERROR)
-            res = self.search_store(name, question, k, filt, div, hyb)
+            if dst and not _distinct_ok(st):
+                raise ValueError(DISTINCT_ERROR)
+            res = self.search_store(name, question, k, filt, div, hyb, dst) if dst else \
+                self.search_store(name, question, k, filt, div, hyb)
             if div:
                 self.last_diversity = "store"
             if hyb:

@@ -89,6 +89,14 @@ def _join_ranges(ranges):
     return out
 
 
+def _concat(a, b):
+    """a followed by b: two device tensors (DeviceIndex.mask_tensor) or two host arrays (host stand-ins)."""
+    if isinstance(a, np.ndarray):
+        return np.concatenate([a, b])
+    import torch
+    return torch.cat([a, b])
+
+
 def _copy_bytes(src_fd, dst_fd, start, n, block=8 << 20):
     """Append bytes [start, start + n) of src to dst (both positioned by the caller for dst)."""
     while n > 0:
@@ -246,6 +254,7 @@ class LocalStore:
         # self.rows by every process (RFX_LEXICAL=1: at open; otherwise at the first lexical() call)
         self._lex = None
         self._lex_dead = set()  # the deleted files whose rows the lexical index has tombstoned
+        self._row_docs = None   # row_docs()'s cached answer for one (generation, version)
 
     # ---- files -------------------------------------------------------------------------------
     def _p(self, name):
@@ -352,6 +361,7 @@ class LocalStore:
         self.version = -1
         self._masks = {}
         self._ranges = {}
+        self._row_docs = None
         self._screen_on = False
         self.data_dir, self.compacted = man.get("data_dir"), man.get("compacted")
         self._prev = None  # (a reload keeps no map from the rows it dropped)
@@ -581,6 +591,7 @@ class LocalStore:
             self.rows, self.files = rows, files
             self.meta_bytes, self.files_bytes, self.tombs = compacted["meta_bytes"], compacted["files_bytes"], 0
             self._masks, self._ranges = {}, {}
+            self._row_docs = None
             if self._screen_on is None:
                 self._screen_on = False  # declined for the old generation: this one may fit
             if hasattr(self.index, "compact"):
@@ -1038,6 +1049,35 @@ class LocalStore:
                     self._ranges.clear()
                 self._ranges[key] = out
             return self._ranges[key]
+
+    def row_docs(self):
+        """(row_doc, doc_ranges, file_ids) of the current row numbering, for the distinct-document search
+        (DeviceIndex.search_distinct): row_doc = the device int32 tensor [rows] of every row's
+        document ordinal, -1 for the rows of deleted files; doc_ranges int64 [n_docs][2] = (first row, rows) of
+        every ordinal; file_ids[ordinal] = the file id.  An ordinal is a file's position in self.files.
+        Cached per (generation, version): after appends alone (the same generation, no new delete) the cached
+        copy is extended by the new rows only; a delete or a compaction rebuilds it.  Another process's
+        commits arrive through _sync like everything else: callers hold a store they got from the registry."""
+        with self.lock:
+            c = self._row_docs
+            if c is not None and c["key"] == (self.generation, self.version):
+                return c["row_doc"], c["doc_ranges"], c["file_ids"]
+            n_rows, n_files = len(self.rows), len(self.files)
+            dead = sum(1 for f in self.files.values() if f["deleted"])
+            grown = c is not None and c["generation"] == self.generation and c["dead"] == dead \
+                and c["rows"] <= n_rows and len(c["file_ids"]) <= n_files
+            row0, doc0 = (c["rows"], len(c["file_ids"])) if grown else (0, 0)
+            fresh = np.full(n_rows - row0, -1, dtype=np.int32)
+            for d, f in enumerate(itertools.islice(self.files.values(), doc0, None), doc0):
+                if not f["deleted"] and f["n"]:
+                    fresh[f["first"] - row0:f["first"] - row0 + f["n"]] = d
+            piece = self.index.mask_tensor(fresh)
+            row_doc = _concat(c["row_doc"], piece) if grown and row0 else piece
+            ranges = np.array([(f["first"], f["n"]) for f in self.files.values()], dtype=np.int64).reshape(-1, 2)
+            self._row_docs = {"key": (self.generation, self.version), "generation": self.generation, "dead": dead,
+                              "rows": n_rows, "row_doc": row_doc, "doc_ranges": ranges, "file_ids": list(self.files),
+                              "extended": bool(grown and row0)}
+            return row_doc, ranges, self._row_docs["file_ids"]
 
     def row_info(self, row, generation=None):
         """(file_id, chunk text, title, uri) of a row, or None for a row this process has no
