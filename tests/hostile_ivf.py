@@ -94,6 +94,9 @@ def _queries(rng, nlist, d, nq, dtype, sizes, noise=NOISE, common=0.0, sign=1.0)
     return stored(sign * _law(rng, lists, d, noise, common), dtype)
 
 
+queries = _queries  # (for corpora built outside this module)
+
+
 def edges(dtype="bf16", nq=33):
     rows, lab, qc, rng = planted(256, EDGE_SIZES, dtype, seed=11)
     q = _queries(rng, len(EDGE_SIZES), 256, nq, dtype, EDGE_SIZES)
