@@ -319,7 +319,13 @@ int rfx_index_screen_read(rfx_index_t h, int64_t tile0, int64_t ntiles, int8_t* 
                           uint32_t* live_h, float* stats_h);
 /* The kernel rfx_search runs for (nq, k): 0 VALU, 1/2/3/6/8/9 exact MFMA scans, 10 the two-pass scan of a
  * batch (9 or more questions, k <= 10), 11 the two-pass scan of 1..8 questions in one launch: every k in
- * 1..64, any dtype, dim 768 or 1024, on an index holding the int8 copy.
+ * 1..64, any dtype, dim 768 or 1024, on an index holding the int8 copy; 12 the wide form of
+ * the two-pass scan: 9 or more questions at k 11..64 (lists of 16, a select at k <= 64, the search's own exact
+ * plan — kernels 1 / 2 / 3 or the VALU scan — as the gated exact pass) on an index holding the
+ * int8 copy, in the (dim, rows, nq, k) cells where it was measured faster (k <= 17 at every size; k <= 40 up to
+ * 300k rows, and for nq > 64 at dim 768; k <= 64 up to 100k rows) and whose plan has at least 64 lists —
+ * otherwise, or with RFX_SCREEN_WIDE=0 in the environment (A/B runs), the exact plan such a batch had before.
+ * rfx_screen_diag serves plans 10 and 12.
  * rfx_search_workspace_bytes(h, nq, k) does not depend on whether the copy exists yet. */
 int rfx_search_plan(rfx_index_t h, int64_t nq, int k, int* out_kernel);
 /* After a two-pass search with workspace ws_d (stream-ordered; this call synchronises): per query

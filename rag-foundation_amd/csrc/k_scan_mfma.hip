@@ -88,7 +88,9 @@ __global__ __launch_bounds__(512) void scan_mfma_kernel(const uint16_t* __restri
                                                         const uint16_t* __restrict__ Qp, int nq,
                                                         int tiles_per_block, int ntiles,
                                                         float* __restrict__ cand_s, int* __restrict__ cand_r,
-                                                        int64_t n_lists, const uint32_t* __restrict__ mask) {
+                                                        int64_t n_lists, const uint32_t* __restrict__ mask,
+                                                        const uint32_t* __restrict__ gate) {
+  if (gate && *gate == 0u) return;  // the wide two-pass scan's gated exact pass at k 11..16 (plan 12)
   using G = MfmaGeom<BN>;
   __shared__ __attribute__((aligned(1024))) uint8_t lds[3 * G::STAGE_BYTES];
 
@@ -314,13 +316,13 @@ void launch_pad_queries(const void* Q, int64_t nq, int64_t nq_pad, int D, int es
 
 template <int DT, int BN>
 static int launch_mfma_kl(const MfmaPlan& p, const uint16_t* X, int nrows, int D, const uint16_t* Qp, int nq,
-                          float* cs, int* cr, hipStream_t st, const uint32_t* mask) {
+                          float* cs, int* cr, hipStream_t st, const uint32_t* mask, const uint32_t* gate) {
   const int ntiles = (nrows + kBM - 1) / kBM;
   dim3 grid(p.blocks, p.q_blocks);
 #define RFX_KL(KV)                                                                                     \
   if (p.k_lane == KV) {                                                                                \
     hipLaunchKernelGGL((scan_mfma_kernel<DT, BN, KV>), grid, dim3(512), 0, st, X, nrows, D, Qp, nq,     \
-                       p.tiles_per_block, ntiles, cs, cr, p.n_lists, mask);                            \
+                       p.tiles_per_block, ntiles, cs, cr, p.n_lists, mask, gate);                          \
     return 0;                                                                                          \
   }
   RFX_KL(4) RFX_KL(8) RFX_KL(10) RFX_KL(16)
@@ -330,10 +332,10 @@ static int launch_mfma_kl(const MfmaPlan& p, const uint16_t* X, int nrows, int D
 
 template <int DT>
 static int launch_mfma_bn(const MfmaPlan& p, const uint16_t* X, int nrows, int D, const uint16_t* Qp, int nq,
-                          float* cs, int* cr, hipStream_t st, const uint32_t* mask) {
-  if (p.bn == 64) return launch_mfma_kl<DT, 64>(p, X, nrows, D, Qp, nq, cs, cr, st, mask);
-  if (p.bn == 128) return launch_mfma_kl<DT, 128>(p, X, nrows, D, Qp, nq, cs, cr, st, mask);
-  return launch_mfma_kl<DT, 256>(p, X, nrows, D, Qp, nq, cs, cr, st, mask);
+                          float* cs, int* cr, hipStream_t st, const uint32_t* mask, const uint32_t* gate) {
+  if (p.bn == 64) return launch_mfma_kl<DT, 64>(p, X, nrows, D, Qp, nq, cs, cr, st, mask, gate);
+  if (p.bn == 128) return launch_mfma_kl<DT, 128>(p, X, nrows, D, Qp, nq, cs, cr, st, mask, gate);
+  return launch_mfma_kl<DT, 256>(p, X, nrows, D, Qp, nq, cs, cr, st, mask, gate);
 }
 
 int launch_scan_mfma_dbg(const MfmaPlan& p, int mode, const void* X, int nrows, int D, const void* Qpad, int nq,
@@ -345,22 +347,22 @@ int launch_scan_mfma_dbg(const MfmaPlan& p, int mode, const void* X, int nrows, 
   const uint16_t* Qh = (const uint16_t*)Qpad;
   if (mode == 1)
     hipLaunchKernelGGL((scan_mfma_kernel<RFX_BF16, 256, 10, 1>), grid, dim3(512), 0, st, Xh, nrows, D, Qh, nq,
-                       p.tiles_per_block, ntiles, cs, cr, p.n_lists, nullptr);
+                       p.tiles_per_block, ntiles, cs, cr, p.n_lists, nullptr, nullptr);
   else if (mode == 2)
     hipLaunchKernelGGL((scan_mfma_kernel<RFX_BF16, 256, 10, 2>), grid, dim3(512), 0, st, Xh, nrows, D, Qh, nq,
-                       p.tiles_per_block, ntiles, cs, cr, p.n_lists, nullptr);
+                       p.tiles_per_block, ntiles, cs, cr, p.n_lists, nullptr, nullptr);
   else
     hipLaunchKernelGGL((scan_mfma_kernel<RFX_BF16, 256, 10, 0>), grid, dim3(512), 0, st, Xh, nrows, D, Qh, nq,
-                       p.tiles_per_block, ntiles, cs, cr, p.n_lists, nullptr);
+                       p.tiles_per_block, ntiles, cs, cr, p.n_lists, nullptr, nullptr);
   return 0;
 }
 
 int launch_scan_mfma(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                     float* cs, int* cr, hipStream_t st, const uint32_t* mask) {
+                     float* cs, int* cr, hipStream_t st, const uint32_t* mask, const uint32_t* gate) {
   if (!p.ok) return -1;
   if (dtype == RFX_BF16)
-    return launch_mfma_bn<RFX_BF16>(p, (const uint16_t*)X, nrows, D, (const uint16_t*)Qpad, nq, cs, cr, st, mask);
-  return launch_mfma_bn<RFX_F16>(p, (const uint16_t*)X, nrows, D, (const uint16_t*)Qpad, nq, cs, cr, st, mask);
+    return launch_mfma_bn<RFX_BF16>(p, (const uint16_t*)X, nrows, D, (const uint16_t*)Qpad, nq, cs, cr, st, mask, gate);
+  return launch_mfma_bn<RFX_F16>(p, (const uint16_t*)X, nrows, D, (const uint16_t*)Qpad, nq, cs, cr, st, mask, gate);
 }
 
 }  // namespace rfx

@@ -89,7 +89,9 @@ __global__ __launch_bounds__(512) void scan_mfma2_kernel(const uint16_t* __restr
                                                          const uint16_t* __restrict__ Qp, int nq, int tiles_per_block,
                                                          int ntiles, uint32_t* __restrict__ tau,
                                                          float* __restrict__ cand_s, int* __restrict__ cand_r,
-                                                         int64_t n_lists, const uint32_t* __restrict__ mask) {
+                                                         int64_t n_lists, const uint32_t* __restrict__ mask,
+                                                         const uint32_t* __restrict__ gate) {
+  if (gate && *gate == 0u) return;  // the wide two-pass scan's gated exact pass at k 11..16 (plan 12)
   __shared__ __attribute__((aligned(1024))) uint8_t lds[kLds];
 
   const int tid = threadIdx.x;
@@ -330,7 +332,7 @@ int launch_scan_mfma2_dbg(const MfmaPlan& p, int mode, const void* X, int nrows,
 #define RFX_M2(MV)                                                                                        \
   if (mode == MV) {                                                                                       \
     hipLaunchKernelGGL((scan_mfma2_kernel<RFX_BF16, 10, MV>), grid, dim3(512), 0, st, Xh, nrows, D, Qh, nq, \
-                       p.tiles_per_block, ntiles, tau, cs, cr, p.n_lists, nullptr);                       \
+                       p.tiles_per_block, ntiles, tau, cs, cr, p.n_lists, nullptr, nullptr);              \
     return 0;                                                                                             \
   }
   RFX_M2(0) RFX_M2(1) RFX_M2(2) RFX_M2(3) RFX_M2(4) RFX_M2(5) RFX_M2(6) RFX_M2(7)
@@ -339,7 +341,8 @@ int launch_scan_mfma2_dbg(const MfmaPlan& p, int mode, const void* X, int nrows,
 }
 
 int launch_scan_mfma2(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask) {
+                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask,
+                      const uint32_t* gate) {
   if (!p.ok) return -1;
   const int ntiles = (nrows + kB2M - 1) / kB2M;
   if (hipMemsetAsync(tau, 0, (size_t)p.nq_pad * sizeof(uint32_t), st) != hipSuccess) return -2;
@@ -349,7 +352,7 @@ int launch_scan_mfma2(const MfmaPlan& p, const void* X, int nrows, int D, int dt
 #define RFX_KL2(DTV, KV)                                                                                  \
   if (dtype == DTV && p.k_lane == KV) {                                                                   \
     hipLaunchKernelGGL((scan_mfma2_kernel<DTV, KV>), grid, dim3(512), 0, st, Xh, nrows, D, Qh, nq,         \
-                       p.tiles_per_block, ntiles, tau, cs, cr, p.n_lists, mask);                          \
+                       p.tiles_per_block, ntiles, tau, cs, cr, p.n_lists, mask, gate);                    \
     return 0;                                                                                             \
   }
   RFX_KL2(RFX_BF16, 4) RFX_KL2(RFX_BF16, 8) RFX_KL2(RFX_BF16, 10) RFX_KL2(RFX_BF16, 16)

@@ -90,7 +90,9 @@ __global__ __launch_bounds__(256, 1) void scan_mfma3_kernel(const uint16_t* __re
                                                             const uint16_t* __restrict__ Qp, int nq,
                                                             int tiles_per_block, int ntiles, uint32_t* __restrict__ tau,
                                                             float* __restrict__ cand_s, int* __restrict__ cand_r,
-                                                            int64_t n_lists, const uint32_t* __restrict__ mask) {
+                                                            int64_t n_lists, const uint32_t* __restrict__ mask,
+                                                            const uint32_t* __restrict__ gate) {
+  if (gate && *gate == 0u) return;  // the wide two-pass scan's gated exact pass at k 11..16 (plan 12)
   constexpr int NKS = D / 16;      // 16-deep MFMA k-steps
   constexpr int NST = D / k3BK;    // stages per tile
   __shared__ __attribute__((aligned(1024))) uint8_t lds[k3Lds];
@@ -266,16 +268,16 @@ __global__ __launch_bounds__(256, 1) void scan_mfma3_kernel(const uint16_t* __re
 #define RFX_K3_INSTANTIATE(DTV, DV, NAME)                                                                  \
   int NAME(int kl, dim3 grid, hipStream_t st, const uint16_t* X, int nrows, const uint16_t* Qp, int nq,      \
            int tiles_per_block, int ntiles, uint32_t* tau, float* cs, int* cr, int64_t n_lists,            \
-           const uint32_t* mask) {                                                                         \
+           const uint32_t* mask, const uint32_t* gate) {                                                   \
     if (kl == 4)                                                                                         \
       hipLaunchKernelGGL((scan_mfma3_kernel<DTV, 4, DV>), grid, dim3(256), 0, st, X, nrows, Qp, nq,        \
-                         tiles_per_block, ntiles, tau, cs, cr, n_lists, mask);                           \
+                         tiles_per_block, ntiles, tau, cs, cr, n_lists, mask, gate);                     \
     else if (kl == 10)                                                                                   \
       hipLaunchKernelGGL((scan_mfma3_kernel<DTV, 10, DV>), grid, dim3(256), 0, st, X, nrows, Qp, nq,       \
-                         tiles_per_block, ntiles, tau, cs, cr, n_lists, mask);                           \
+                         tiles_per_block, ntiles, tau, cs, cr, n_lists, mask, gate);                     \
     else if (kl == 16)                                                                                   \
       hipLaunchKernelGGL((scan_mfma3_kernel<DTV, 16, DV>), grid, dim3(256), 0, st, X, nrows, Qp, nq,       \
-                         tiles_per_block, ntiles, tau, cs, cr, n_lists, mask);                           \
+                         tiles_per_block, ntiles, tau, cs, cr, n_lists, mask, gate);                     \
     else                                                                                                 \
       return -1;                                                                                         \
     return 0;                                                                                            \

@@ -26,6 +26,12 @@
 //     batch) when a dropped A reaches a_k − e2 or the survivors overflow its buffer.
 // Dead rows (tombstones, the NaN tail, rows a metadata filter excludes) carry code 0 and a clear
 // bit in the tile's live word; the slow path skips them, so they never raise a_k.
+// The wide form (top-k 11..64 on lists of KL = 16 < k; plan 12) replaces the pruning bound by one that does not
+// need KL >= k ("the wide form" below, with its proof); lists + drop stay the contract with the select: a lane
+// keeps its 16 best and the best A it did not keep, the select (k <= 64) takes a_k' over the kept candidates
+// (a_k' <= a_k, so the survivor set A >= a_k' - e2 only grows) and sets the gate when a drop reaches a_k' - e2,
+// when the kept candidates overflow its LDS, or when fewer than k are kept although something was dropped.
+// Padded queries, tombstones, the NaN tail and row masks are handled by the same code as in kernel 10.
 //
 // Layout and schedule follow kernel 6 (k_scan_mfma6.h) at half the bytes: workgroup = 8 waves ×
 // 32 resident queries (B fragments: D / 64 k-steps × 2 query blocks × 16 B = 96 VGPRs at d 768),
@@ -56,6 +62,7 @@ constexpr int kSlot = kTM * kRowB;        // 8 KB: 32 rows × 256 codes
 constexpr int kRing = RFX_K10_RING;       // slots; RING - 1 stages in flight
 constexpr int kGPW = 1;                   // LDS-DMA pieces per wave per stage (8 KB / 1 KB / 8 waves)
 constexpr int kTauW = 16;                 // u32 per query in the threshold table: 16 slots (tau_kth)
+constexpr int kWideKL = 16;               // list length of the wide form (top-k 11..64)
 constexpr int kTauBytes = kQG * kTauW * 4;  // 16 KB
 constexpr int kTauGPW = kTauBytes / 1024 / kWaves;
 constexpr int kMR = 8;  // tile-metadata slots (1 KB each: 64 lane copies of the 16-B record)
@@ -85,10 +92,12 @@ template <int KL, int RING, int NW = kWaves>
 constexpr int ctr_off() { return list_off<RING, NW>(); }
 // the list area (debug MODE 1024's LDS lists) exists in the 8-wave kernel; the 2-wave kernel keeps only the
 // 128 B of counters, so two workgroups fit a CU's LDS
-template <int KL, int RING, int NW = kWaves>
-constexpr int lds_bytes() { return list_off<RING, NW>() + (NW == kWaves ? kWaves * KL * 64 * 8 : 128); }
+// (nor has the wide form, WIDE below: sixteen entries a lane would not fit beside a 10-slot ring)
+template <int KL, int RING, int NW = kWaves, bool LISTS = true>
+constexpr int lds_bytes() { return list_off<RING, NW>() + (NW == kWaves && LISTS ? kWaves * KL * 64 * 8 : 128); }
 static_assert(lds_bytes<10, 12>() <= 163840, "LDS budget");
 static_assert(2 * lds_bytes<16, 8, 2>() <= 163840, "two 2-wave workgroups per CU");
+static_assert(lds_bytes<16, 10, kWaves, false>() <= 163840, "LDS budget of the wide 8-wave form");
 
 // spin (s_sleep) until the LDS counter reaches target; bounded, so a counting error can never hang the
 // GPU (the result would be wrong, and the tests would say so)
@@ -126,8 +135,7 @@ __device__ __forceinline__ bool tau_refresh_tile(int it) {
 // to the KL-th best (simulated on 10M Gaussian scores, 512 lists: 14.6 rows above the bound against
 // 26.2 for k = 10), so fewer rows reach bound - e2 and fewer tiles take the slow path.  Bitonic sort of
 // the 16 values, descending (80 compare-exchanges; the refresh runs every 4th tile).
-template <int KL>
-__device__ __forceinline__ uint32_t kth16(uint32_t (&v)[16]) {
+__device__ __forceinline__ void sort16_desc(uint32_t (&v)[16]) {
 #pragma unroll
   for (int k = 2; k <= 16; k <<= 1)
 #pragma unroll
@@ -142,11 +150,13 @@ __device__ __forceinline__ uint32_t kth16(uint32_t (&v)[16]) {
           v[l] = desc ? min(a, b) : max(a, b);
         }
       }
-  return v[KL - 1];
 }
 template <int KL>
-__device__ __forceinline__ uint32_t tau_kth(const uint8_t* p) {
-  uint32_t v[16];
+__device__ __forceinline__ uint32_t kth16(uint32_t (&v)[16]) {
+  sort16_desc(v);
+  return v[KL - 1];
+}
+__device__ __forceinline__ void tau_load16(const uint8_t* p, uint32_t (&v)[16]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const uint4 a = *(const uint4*)(p + 16 * i);
@@ -155,7 +165,42 @@ __device__ __forceinline__ uint32_t tau_kth(const uint8_t* p) {
     v[4 * i + 2] = a.z;
     v[4 * i + 3] = a.w;
   }
+}
+template <int KL>
+__device__ __forceinline__ uint32_t tau_kth(const uint8_t* p) {
+  uint32_t v[16];
+  tau_load16(p, v);
   return kth16<KL>(v);
+}
+
+// ---- the wide form (WIDE: 11 <= k <= 64 with lists of KL = 16) -------------------------------
+// KL >= k no longer holds, so neither the own list's KL-th best nor the KL-th largest slot bounds a_k.  The
+// bound that does, on the same 16 slots and the same counted slot-table stream:
+//   m = ceil(k / 16) (1..4), t = ceil(k / m) (<= 16).  List j publishes its m-th best A (not its best) to slot
+//   j % 16 by atomic max, once it holds m entries.  A slot's value v was published by ONE list, which then
+//   held m distinct live rows with A >= v (a list only ever improves, so it still does).  Different slots
+//   were written by different lists (j % 16 differs), and lists are disjoint row sets.  So at the t-th largest
+//   slot value b there are t lists with m rows each at A >= b: t m >= k distinct live rows, hence b <= a_k.
+//   An empty slot is 0 (below every orderable score): when fewer than t slots are filled the t-th largest
+//   is 0, "no bound".  A stale table only gives a smaller b: still a lower bound (the thin refresh applies).
+// For k <= 16 this is kernel 10's rule itself (m = 1, t = k), and the own list's 16th best is a bound as
+// before (16 >= k); for k > 16 the own term is dropped.  The price of staying on 16 slots is a looser bound
+// than one slot per row would give (m-th best of single lists): more rows are looked at, none is lost.
+__device__ __forceinline__ int wide_m(int k) { return (k + 15) >> 4; }
+__device__ __forceinline__ int wide_t(int k) { return (k + wide_m(k) - 1) / wide_m(k); }
+// position t - 1 (wave-uniform) of the slots sorted best first = the largest of positions t - 1 .. 15: a
+// compare and a max per slot (a select chain on t becomes an indexed read of the array, through scratch)
+__device__ __forceinline__ uint32_t sorted16_at(const uint32_t (&v)[16], int t) {
+  uint32_t r = 0u;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) r = max(r, i >= t - 1 ? v[i] : 0u);
+  return r;
+}
+__device__ __forceinline__ uint32_t tau_kth_wide(const uint8_t* p, int t) {
+  uint32_t v[16];
+  tau_load16(p, v);
+  sort16_desc(v);
+  return sorted16_at(v, t);
 }
 
 __device__ __forceinline__ v4i32 mfma_i8(const uint4& a, const uint4& b, const v4i32& c) {
@@ -276,13 +321,21 @@ __device__ __forceinline__ void fold_trip(const v4i32 (&a)[4], float st, int rba
 // PUBCH (kModePubOnChange, production since round 5): the list's best is published only when it rose above what this lane
 // published last (the slot table holds the same values either way: an atomic max with a value already
 // published is a no-op), so a slow-path entry that does not raise the list's best issues no atomic.
-template <int KL, bool PUBCH = false>
+// WIDE: the list's wm-th best is what it publishes (0 while it holds fewer: a no-op), and its KL-th best
+// tightens the own bound only when KL >= k (own_ok); see "the wide form" above.
+template <int KL, bool PUBCH = false, bool WIDE = false>
 __device__ __forceinline__ void fold_end(const uint64_t (&L)[KL], uint32_t& thr_o, bool pub, v4i32 tau_rsrc,
-                                         uint32_t slot_voff, uint32_t& pubd) {
+                                         uint32_t slot_voff, uint32_t& pubd, int wm = 1, bool own_ok = true) {
   if (pub) {
-    const uint32_t own = (uint32_t)(L[KL - 1] >> 32);
+    const uint32_t own = !WIDE || own_ok ? (uint32_t)(L[KL - 1] >> 32) : 0u;
     thr_o = own > thr_o ? own : thr_o;
-    const uint32_t best = (uint32_t)(L[0] >> 32);
+    uint32_t best = (uint32_t)(L[0] >> 32);
+    if constexpr (WIDE) {
+      static_assert(KL >= 4, "m <= 4");
+      best = 0u;  // entry wm - 1 of the sorted list = the largest of entries wm - 1 .. 3 (as sorted16_at)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) best = max(best, i >= wm - 1 ? (uint32_t)(L[i] >> 32) : 0u);
+    }
     if (!PUBCH || best > pubd) {
       batomic_umax(tau_rsrc, slot_voff, best);
       pubd = best;
@@ -348,11 +401,11 @@ __device__ __forceinline__ void fold_sorted(const v4i32 (&a)[4], float st, int r
   drop_o = max(drop_o, d);
 }
 constexpr int kSortMergeTrips = 8;  // (a merge costs about as much VALU as 8 trips)
-template <int KL, bool REG = true, bool FMASK = false, bool SORTM = false, bool PUBCH = false>
+template <int KL, bool REG = true, bool FMASK = false, bool SORTM = false, bool PUBCH = false, bool WIDE = false>
 __device__ __forceinline__ void fold_screen(const v4i32 (&a)[4], float st, uint32_t bits, uint64_t* Ls, uint64_t (&L)[KL],
                                             uint32_t& thr_o,
                                             float e2, uint32_t& drop_o, int rbase, v4i32 tau_rsrc, uint32_t slot_voff,
-                                            uint32_t& pubd) {
+                                            uint32_t& pubd, int wm = 1, bool own_ok = true) {
   if constexpr (REG) {
     bool pub;
     uint32_t pm = FMASK ? fold_mask(a, st, bits, thr_o, e2, pub) : fold_mask_int(a, st, bits, thr_o, e2, pub);
@@ -370,7 +423,7 @@ __device__ __forceinline__ void fold_screen(const v4i32 (&a)[4], float st, uint3
       // trip per position some lane passes at
       while (pm) fold_trip<KL>(a, st, rbase, pm, L, drop_o);
     }
-    fold_end<KL, PUBCH>(L, thr_o, pub, tau_rsrc, slot_voff, pubd);
+    fold_end<KL, PUBCH, WIDE>(L, thr_o, pub, tau_rsrc, slot_voff, pubd, wm, own_ok);
   } else {
     const float thr = thr_o ? unord(thr_o) - e2 : -__builtin_inff();
 #pragma unroll
@@ -496,15 +549,17 @@ constexpr int kModeRunAddr = 67108864;   // the stream's source and ring slot as
 constexpr int kModeFragOff = 134217728;  // fragment reads: one lane-constant offset per k-step + the slot's bytes
 constexpr int kModeThin = kThinBit;      // slot-table refresh every 16th tile from tile kThinFrom on
 constexpr int kModeThin64 = kThin64Bit;  // ... every 64th
-template <int KL, int D, bool MASK, int RING = kRing, int MODE = 0, int NW = kWaves>
-__global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* __restrict__ X, const uint4* __restrict__ tmeta,
-                                                             const uint32_t* __restrict__ stats,
-                                                             const int8_t* __restrict__ Qc, const float* __restrict__ qe2,
-                                                             int nq, int ntiles, uint32_t* __restrict__ tau,
-                                                             float* __restrict__ cand_s, int* __restrict__ cand_r,
-                                                             uint32_t* __restrict__ drops, int64_t n_lists,
-                                                             const uint32_t* __restrict__ mask, uint32_t* __restrict__ xb,
-                                                             uint32_t* __restrict__ xw) {
+// WIDE (kreq = the requested k, 11..64; otherwise unused): the bound of "the wide form" above.  The kernels
+// proper are the two wrappers after the body.
+template <int KL, int D, bool MASK, int RING, int MODE, int NW, bool WIDE>
+__device__ __forceinline__ void scan_screen_body(const int8_t* __restrict__ X, const uint4* __restrict__ tmeta,
+                                                 const uint32_t* __restrict__ stats,
+                                                 const int8_t* __restrict__ Qc, const float* __restrict__ qe2,
+                                                 int nq, int ntiles, uint32_t* __restrict__ tau,
+                                                 float* __restrict__ cand_s, int* __restrict__ cand_r,
+                                                 uint32_t* __restrict__ drops, int64_t n_lists,
+                                                 const uint32_t* __restrict__ mask, uint32_t* __restrict__ xb,
+                                                 uint32_t* __restrict__ xw, int kreq) {
   constexpr int NKS = D / 64;    // 64-deep k-steps per tile
   constexpr int NST = D / kSK;   // stages per tile
   constexpr int KPS = kSK / 64;  // k-steps per stage (4)
@@ -516,7 +571,10 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
   constexpr int GPW = 8 / NW;          // LDS-DMA pieces per wave per stage (8 KB / 1 KB / NW)
   constexpr int TAUB = tau_bytes_nw<NW>();
   static_assert(TAUB / 1024 / NW == kTauGPW, "slot-table DMA pieces per wave");
-  __shared__ __attribute__((aligned(1024))) uint8_t lds[lds_bytes<KL, RING, NW>()];
+  static_assert(!WIDE || (MODE & (1024 | 256 | 32 | kModeFold2)) == 0, "the wide form has the production fold only");
+  __shared__ __attribute__((aligned(1024))) uint8_t lds[lds_bytes<KL, RING, NW, !WIDE>()];
+  const int wm = WIDE ? wide_m(kreq) : 1, wt = WIDE ? wide_t(kreq) : KL;
+  const bool own_ok = !WIDE || kreq <= KL;
   constexpr int kTauOff = tau_off<RING>();
   constexpr int kMetaOff = meta_off<RING>();
   constexpr int kListOff = list_off<RING, NW>();
@@ -577,7 +635,7 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
     for (int i = 0; i < TAUB / 16 / NT; ++i) tz[tid + NT * i] = uint4{0u, 0u, 0u, 0u};
   }
   uint64_t* const Ls = (uint64_t*)(lds + kListOff) + (w * KL) * 64 + lane;  // debug MODE 1024's list
-  if constexpr (NW == kWaves)
+  if constexpr (NW == kWaves && !WIDE)
 #pragma unroll
     for (int i = 0; i < KL; ++i) Ls[i * 64] = 0ull;
   uint32_t* const ready = (uint32_t*)(lds + ctr_off<KL, RING, NW>());  // MODE 32768: [RING] pieces landed
@@ -928,10 +986,10 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
           }
         } else {
           fold_screen<KL, (MODE & 1024) == 0, (MODE & kModeFloatMask) != 0, (MODE & kModeSortMerge) != 0,
-                      (MODE & kModePubOnChange) != 0>(
+                      (MODE & kModePubOnChange) != 0, WIDE>(
               acc4, st, lw >> (8 * half), Ls, Lr, thr, e2, drop,
                                                                               tile * kTM + 8 * half,
-                                              tau_rsrc, slot_voff, pubd);
+                                              tau_rsrc, slot_voff, pubd, wm, own_ok);
         }
         set_bounds();
         if constexpr ((MODE & 2048) != 0) __builtin_amdgcn_s_setprio(0);
@@ -943,7 +1001,10 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
   auto tile_body = [&](const int it, v4i32(&acc4)[4], v4i32(&accp)[4], const bool prev) {
     const int gbase = it * NST;
     if (it >= TBD && tau_refresh_tile<MODE>(it - TBD)) {
-      thr = max(thr, (MODE & 256) != 0 ? tau_min<KL>(tq) : tau_kth<KL>(tq));
+      if constexpr (WIDE)
+        thr = max(thr, tau_kth_wide(tq, wt));
+      else
+        thr = max(thr, (MODE & 256) != 0 ? tau_min<KL>(tq) : tau_kth<KL>(tq));
       set_bounds();
     }
     // metadata records younger than stage g+1's piece at stage s's wait: stages h in g+1 .. g+RING-1
@@ -1110,7 +1171,13 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
 #pragma unroll
     for (int j = 0; j < 16; ++j)
       sl[j] = j >= kSlots ? 0u : __hip_atomic_load(tau + (int64_t)q * kTauW + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    uint32_t m = kth16<KL>(sl);
+    uint32_t m;
+    if constexpr (WIDE) {
+      sort16_desc(sl);
+      m = sorted16_at(sl, wt);
+    } else {
+      m = kth16<KL>(sl);
+    }
     if constexpr ((MODE & 256) != 0) {
       m = 0xffffffffu;
 #pragma unroll
@@ -1149,6 +1216,29 @@ __global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* _
     }
   }
 #endif
+}
+
+template <int KL, int D, bool MASK, int RING = kRing, int MODE = 0, int NW = kWaves>
+__global__ __launch_bounds__(64 * NW, 1) void scan_screen_kernel(const int8_t* __restrict__ X, const uint4* __restrict__ tmeta,
+                                                             const uint32_t* __restrict__ stats,
+                                                             const int8_t* __restrict__ Qc, const float* __restrict__ qe2,
+                                                             int nq, int ntiles, uint32_t* __restrict__ tau,
+                                                             float* __restrict__ cand_s, int* __restrict__ cand_r,
+                                                             uint32_t* __restrict__ drops, int64_t n_lists,
+                                                             const uint32_t* __restrict__ mask, uint32_t* __restrict__ xb,
+                                                             uint32_t* __restrict__ xw) {
+  scan_screen_body<KL, D, MASK, RING, MODE, NW, false>(X, tmeta, stats, Qc, qe2, nq, ntiles, tau, cand_s, cand_r, drops,
+                                                       n_lists, mask, xb, xw, KL);
+}
+// the wide form: lists of 16 for a requested k of 11..64 (plan 12)
+template <int D, bool MASK, int RING, int MODE, int NW>
+__global__ __launch_bounds__(64 * NW, 1) void scan_screen_wide_kernel(
+    const int8_t* __restrict__ X, const uint4* __restrict__ tmeta, const uint32_t* __restrict__ stats,
+    const int8_t* __restrict__ Qc, const float* __restrict__ qe2, int nq, int ntiles, uint32_t* __restrict__ tau,
+    float* __restrict__ cand_s, int* __restrict__ cand_r, uint32_t* __restrict__ drops, int64_t n_lists,
+    const uint32_t* __restrict__ mask, uint32_t* __restrict__ xb, uint32_t* __restrict__ xw, int kreq) {
+  scan_screen_body<kWideKL, D, MASK, RING, MODE, NW, true>(X, tmeta, stats, Qc, qe2, nq, ntiles, tau, cand_s, cand_r, drops,
+                                                      n_lists, mask, xb, xw, kreq);
 }
 
 // Production schedule (round 5): one counted wait + barrier per TILE (kModeTileBarrier) over a 10-slot ring —
@@ -1210,6 +1300,23 @@ constexpr int w2_mode() { return D == 768 ? kProdMode : (kModePubOnChange | kLea
                          ntiles, tau, cs, cr, dr, n_lists, mask, xb, xw);                                    \
     else                                                                                                    \
       return -1;                                                                                            \
+    return 0;                                                                                               \
+  }
+
+
+// the wide form's units (k10k_*.hip: NWV 8, kProdRing / kProdMode; k10kw2_*.hip: NWV 2, the 2-wave ring and mode),
+// with and without a filter mask; k = the requested top-k (11..64)
+#define RFX_K10_INSTANTIATE_WIDE(DV, NWV, RV, MV, NAME)                                                        \
+  int NAME(int k, dim3 grid, hipStream_t st, const int8_t* X, const uint4* tm, const uint32_t* sts,            \
+           const int8_t* Qc, const float* qe2, int nq, int ntiles, uint32_t* tau, float* cs, int* cr,          \
+           uint32_t* dr, int64_t n_lists, const uint32_t* mask, uint32_t* xb, uint32_t* xw) {               \
+    if (k < 11 || k > 64) return -1;                                                                        \
+    if (!mask)                                                                                              \
+      hipLaunchKernelGGL((scan_screen_wide_kernel<DV, false, RV, MV, NWV>), grid, dim3(64 * NWV), 0, st, X, tm, \
+                         sts, Qc, qe2, nq, ntiles, tau, cs, cr, dr, n_lists, mask, xb, xw, k);               \
+    else                                                                                                    \
+      hipLaunchKernelGGL((scan_screen_wide_kernel<DV, true, RV, MV, NWV>), grid, dim3(64 * NWV), 0, st, X, tm,  \
+                         sts, Qc, qe2, nq, ntiles, tau, cs, cr, dr, n_lists, mask, xb, xw, k);               \
     return 0;                                                                                               \
   }
 

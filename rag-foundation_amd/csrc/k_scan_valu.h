@@ -474,8 +474,8 @@ __global__ __launch_bounds__(256) void scan_valu_kernel(const uint8_t* __restric
                                                         int* __restrict__ cand_r, int n_lists,
                                                         const uint32_t* __restrict__ mask,
                                                         uint32_t* __restrict__ tau, FusedOut fo) {
-  if constexpr (FUSED)  // gated (the two-pass scan's fallback): the whole grid returns together
-    if (fo.gate && __hip_atomic_load(fo.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;
+  // gated (the two-pass scan's fallback, one-launch or plain): the whole grid returns together
+  if (fo.gate && __hip_atomic_load(fo.gate, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) return;
   scan_valu_body<DT, NQT, K, VPL, FUSED>(X, nrows, D, Qf, nq, rows_per_wave, cand_s, cand_r, n_lists, mask, tau, fo,
                                          (int)blockIdx.x, (int)gridDim.x);
 }

@@ -122,8 +122,8 @@ static int launch_valu(const ValuPlan& p, const void* X, int nrows, int D, int d
 }
 
 int launch_scan_valu(const ValuPlan& p, const void* X, int nrows, int D, int dtype, const float* Qf, int nq,
-                     float* cs, int* cr, hipStream_t st, const uint32_t* mask, uint32_t* tau) {
-  return launch_valu(p, X, nrows, D, dtype, Qf, nq, cs, cr, st, mask, tau, FusedOut{nullptr, 0, nullptr, nullptr});
+                     float* cs, int* cr, hipStream_t st, const uint32_t* mask, uint32_t* tau, const uint32_t* gate) {
+  return launch_valu(p, X, nrows, D, dtype, Qf, nq, cs, cr, st, mask, tau, FusedOut{nullptr, 0, nullptr, nullptr, gate});
 }
 
 int launch_search_valu_fused(const ValuPlan& p, const void* X, int nrows, int D, int dtype, const void* Q, int nq,

@@ -30,6 +30,10 @@ RFX_K10_DECL(launch_768)
 RFX_K10_DECL(launch_1024)
 RFX_K10_DECL(launch_768_w2)
 RFX_K10_DECL(launch_1024_w2)
+// the wide form (k10k_768.hip, k10kw2_*.hip): the first argument is the requested k (11..64)
+RFX_K10_DECL(launch_768_wide)
+RFX_K10_DECL(launch_768_wide_w2)
+RFX_K10_DECL(launch_1024_wide_w2)
 }  // namespace k10
 namespace k10q {
 RFX_K10_DECL(launch_768)
@@ -372,6 +376,20 @@ __global__ __launch_bounds__(512) void screen_select_kernel(const float* __restr
   sel::select_body<DT, D>(cs, cr, drops, n_lists, list_len, qe2, Q, X, k, row_offset, out_s, out_r, out_rec, gate, diag,
                           force, (int64_t)blockIdx.x, sl);
 }
+// the wide form's select (k <= 64, kSelCapWide kept candidates): the same body over the larger LDS image
+template <int DT, int D>
+__global__ __launch_bounds__(512) void screen_select_wide_kernel(const float* __restrict__ cs, const int* __restrict__ cr,
+                                                                 const uint32_t* __restrict__ drops, int64_t n_lists,
+                                                                 int list_len, const float* __restrict__ qe2,
+                                                                 const uint8_t* __restrict__ Q,
+                                                                 const uint8_t* __restrict__ X, int k, int64_t row_offset,
+                                                                 float* __restrict__ out_s, int64_t* __restrict__ out_r,
+                                                                 sel::Rec* __restrict__ out_rec, uint32_t* __restrict__ gate,
+                                                                 int* __restrict__ diag, int force) {
+  __shared__ sel::SelLdsT<sel::kSelCapWide> sl;
+  sel::select_body<DT, D, sel::kSelCapWide>(cs, cr, drops, n_lists, list_len, qe2, Q, X, k, row_offset, out_s, out_r,
+                                            out_rec, gate, diag, force, (int64_t)blockIdx.x, sl);
+}
 
 }  // namespace
 
@@ -431,12 +449,30 @@ int screen_w2_blocks() {
   return v;
 }
 
+// RFX_SCREEN_WIDE=0 (A/B runs): batches at k 11..64 keep the exact plans they had before the wide form;
+// =2 (measuring, tools/bench_topk_batch.py): the wide form also in the cells the plan leaves to the exact plans
+// the wide form's largest planned k above 1M rows (d 768; measured at 10M rows)
+constexpr int kWideKCap10MW2 = 17, kWideKCap10MW8 = 40;
+static int screen_wide_mode() {
+  static const int v = [] {
+    const char* e = getenv("RFX_SCREEN_WIDE");
+    return e && e[0] == '0' ? 0 : (e && e[0] == '2' ? 2 : 1);
+  }();
+  return v;
+}
+bool screen_wide_enabled() { return screen_wide_mode() != 0; }
+
+// k <= 10: kernel 10 as ever.  k 11..64 (the wide form, plan 12, nq >= 9): lists of 16; d 768 splits the batch as
+// kernel 10 does (2 waves up to 64 questions, 8 waves above), d 1024 runs the 2-wave kernel on every 64 questions
+// (its 8-wave form with sixteen entries a lane does not fit the register file without scratch).  Planned only
+// with at least 64 lists: the bound needs 16 filled slots (and n_lists >= k); a smaller store keeps its exact plan.
 MfmaPlan plan_scan_screen(int64_t nrows, int D, int dtype, int64_t nq, int k, int max_blocks) {
   MfmaPlan p{};
   p.ok = screen_supported(D, dtype) && nrows > 0;
-  p.k_lane = k <= 4 ? 4 : (k <= 10 ? 10 : -1);
-  if (p.k_lane < 0) p.ok = false;
-  const bool w2 = nq <= k10::kQGSmall;
+  const bool wide = k > 10;
+  p.k_lane = k <= 4 ? 4 : (k <= 10 ? 10 : (k <= 64 ? k10::kWideKL : -1));
+  if (p.k_lane < 0 || (wide && (nq <= 8 || !screen_wide_enabled()))) p.ok = false;
+  const bool w2 = nq <= k10::kQGSmall || (wide && D == 1024);
   p.bn = w2 ? k10::kQGSmall : k10::kQG;
   p.q_blocks = (int)((nq + p.bn - 1) / p.bn);
   p.nq_pad = (int64_t)p.q_blocks * p.bn;
@@ -456,8 +492,32 @@ MfmaPlan plan_scan_screen(int64_t nrows, int D, int dtype, int64_t nq, int k, in
   ranges = std::max<int64_t>(std::min<int64_t>(ranges, ntiles), 1);
   p.blocks = (int)ranges;
   p.tiles_per_block = (int)((ntiles + ranges - 1) / ranges);
-  p.lists_per_block = (!w2 && D == 768 && screen_q64()) ? 1 : 2;  // (the 64-queries-per-wave kernel: one list)
+  p.lists_per_block = (!w2 && !wide && D == 768 && screen_q64()) ? 1 : 2;  // (the 64-queries-per-wave kernel: one list)
   p.n_lists = (int64_t)p.blocks * p.lists_per_block;
+  if (wide && p.n_lists < 64) p.ok = false;
+  // Measured cells only (tools/bench_topk_batch.py, the wide form against the plan the search
+  // has without it, same call).  On 16 slots the bound loosens as k and the store grow; past kSelCapWide kept
+  // candidates a batch falls back and pays the screen on top of its exact plan.  The screen reads the int8 copy
+  // only, so a cell is (d, rows, kernel form, k), not the dtype.  k_cap = the largest k that won by more than the
+  // run-to-run spread at the measured size at or above the store's:
+  //   rows <= 100k: 64 (d 768, every form; d 1024 is not timed there, only checked free of fallbacks by the tests)      rows <= 300k: 40 (d 768)      rows <= 1M: 17 in the 2-wave form, 40 in
+  //   the 8-wave form (d 768);  d 1024 above 100k rows: 17 (measured at 1M);  above 1M rows (measured at 10M): the same, kWideKCap10M*.
+  // d 1024 at nq > 64 runs the 2-wave kernel once per 64 questions and lost to kernel 3 at k <= 16 (1.59 against
+  // 1.37 ms at 1M rows): not planned there.  RFX_SCREEN_WIDE=2 (measuring) plans every cell.
+  if (wide && screen_wide_mode() != 2) {
+    int k_cap;
+    if (nrows <= 100000)
+      k_cap = 64;
+    else if (D == 1024)
+      k_cap = 17;
+    else if (nrows <= 300000)
+      k_cap = 40;
+    else if (nrows <= 1000000)
+      k_cap = w2 ? 17 : 40;
+    else
+      k_cap = w2 ? kWideKCap10MW2 : kWideKCap10MW8;
+    if (k > k_cap || (D == 1024 && nq > k10::kQGSmall && k <= 16)) p.ok = false;
+  }
   return p;
 }
 
@@ -509,14 +569,18 @@ void launch_screen_queries(const void* Q, int dtype, int D, int64_t nq, int64_t 
 
 int launch_scan_screen(const MfmaPlan& p, const int8_t* codes, const void* tmeta, const uint32_t* stats, int nrows, int D,
                        const int8_t* Qc, const float* qe2, int nq, uint32_t* tau, float* cs, int* cr, uint32_t* drops,
-                       hipStream_t st, const uint32_t* mask) {
+                       hipStream_t st, const uint32_t* mask, int k) {
   if (!p.ok || (D != 768 && D != 1024)) return -1;
   const int ntiles = (nrows + k10::kTM - 1) / k10::kTM;
   dim3 grid(p.blocks, p.q_blocks);
-  auto f = p.bn == k10::kQGSmall ? (D == 768 ? k10::launch_768_w2 : k10::launch_1024_w2)
+  const bool wide = p.k_lane == k10::kWideKL;  // (k: the requested top-k, read by the wide form only)
+  if (wide && (k < 11 || k > 64 || (D == 1024 && p.bn != k10::kQGSmall))) return -1;
+  auto f = wide ? (p.bn != k10::kQGSmall ? k10::launch_768_wide
+                                         : (D == 768 ? k10::launch_768_wide_w2 : k10::launch_1024_wide_w2))
+           : p.bn == k10::kQGSmall ? (D == 768 ? k10::launch_768_w2 : k10::launch_1024_w2)
            : p.lists_per_block == 1 ? k10q::launch_768
                                     : (D == 768 ? k10::launch_768 : k10::launch_1024);
-  return f(p.k_lane, grid, st, codes, (const uint4*)tmeta, stats, Qc, qe2, nq, ntiles, tau, cs, cr, drops, p.n_lists,
+  return f(wide ? k : p.k_lane, grid, st, codes, (const uint4*)tmeta, stats, Qc, qe2, nq, ntiles, tau, cs, cr, drops, p.n_lists,
            mask, tau + p.nq_pad * k10::kTauW, xcd_weights_device_ptr());
 }
 
@@ -525,11 +589,19 @@ int launch_screen_select(const float* cs, const int* cr, const uint32_t* drops, 
                          int64_t row_offset, float* out_s, int64_t* out_r, void* out_rec, uint32_t* gate, int* diag,
                          int force, hipStream_t st) {
   if (nq <= 0) return 0;
-  if (k < 1 || k > sel::kSelK) return -1;
+  const bool wide = k > sel::kSelK || list_len == k10::kWideKL;  // (plan 12: k 11..64 over lists of 16)
+  if (k < 1 || k > (wide ? sel::kSelKWide : sel::kSelK)) return -1;
 #define RFX_SEL(DTV, DV)                                                                                          \
-  hipLaunchKernelGGL((screen_select_kernel<DTV, DV>), dim3((unsigned)nq), dim3(512), 0, st, cs, cr, drops, n_lists, \
-                     list_len, qe2, (const uint8_t*)Q, (const uint8_t*)X, k, row_offset, out_s, out_r,             \
-                     (sel::Rec*)out_rec, gate, diag, force)
+  do {                                                                                                            \
+  if (wide)                                                                                                       \
+    hipLaunchKernelGGL((screen_select_wide_kernel<DTV, DV>), dim3((unsigned)nq), dim3(512), 0, st, cs, cr, drops, \
+                       n_lists, list_len, qe2, (const uint8_t*)Q, (const uint8_t*)X, k, row_offset, out_s, out_r, \
+                       (sel::Rec*)out_rec, gate, diag, force);                                                    \
+  else                                                                                                            \
+    hipLaunchKernelGGL((screen_select_kernel<DTV, DV>), dim3((unsigned)nq), dim3(512), 0, st, cs, cr, drops,      \
+                       n_lists, list_len, qe2, (const uint8_t*)Q, (const uint8_t*)X, k, row_offset, out_s, out_r, \
+                       (sel::Rec*)out_rec, gate, diag, force);                                                    \
+  } while (0)
   if (dtype == RFX_BF16 && D == 768)
     RFX_SEL(RFX_BF16, 768);
   else if (dtype == RFX_BF16)

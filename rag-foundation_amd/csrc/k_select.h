@@ -26,6 +26,10 @@ __device__ __forceinline__ float widen(uint16_t h) {
 
 constexpr int kSelCap = 2048;  // kept candidates per query held in LDS; more -> fallback (8 waves x 256)
 constexpr int kSelK = 16;      // k <= kSelK (kernel 10 plans k <= 10)
+// The wide form (plan 12): k <= 64 (res_key holds 64) over lists of 16 under a looser pruning
+// bound, so more kept candidates per query: a larger LDS image (80 KB), the same steps.
+constexpr int kSelCapWide = 4096;
+constexpr int kSelKWide = 64;
 
 #ifndef RFX_SEL_T
 #define RFX_SEL_T(i)
@@ -33,15 +37,17 @@ constexpr int kSelK = 16;      // k <= kSelK (kernel 10 plans k <= 10)
 
 // the select's LDS: survivor j's rank key (orderable fl32 of the exact f64 sum) << 32 | ~row — larger key =
 // better under (score desc, row asc), so a rank is one 64-bit compare per survivor, no branches
-struct SelLds {
-  uint64_t skey[kSelCap];
+template <int CAP>
+struct SelLdsT {
+  uint64_t skey[CAP];
   uint64_t res_key[64];                           // the answer, written out by one wave
-  __attribute__((aligned(16))) float ca[kSelCap];  // screen score A of kept candidate i
-  int crow[kSelCap];                              // its row
-  int srow[kSelCap];                              // survivor j's row
+  __attribute__((aligned(16))) float ca[CAP];  // screen score A of kept candidate i
+  int crow[CAP];                              // its row
+  int srow[CAP];                              // survivor j's row
   int n_c, n_sv, fail;
   float ak;
 };
+using SelLds = SelLdsT<kSelCap>;
 
 // one 16-B chunk's products added to acc in f64 (f32 products of bf16 / f16 values are exact; f32 values are
 // multiplied in f64, also exact)
@@ -63,14 +69,14 @@ __device__ __forceinline__ void chunk_dot(double& acc, const uint4& x, const uin
 }
 
 // Returns false (and sets the gate) when the query's survivors may be incomplete: nothing written.
-template <int DT, int D>
+template <int DT, int D, int CAP = kSelCap>
 __device__ __forceinline__ bool select_body(const float* __restrict__ cs, const int* __restrict__ cr,
                                             const uint32_t* __restrict__ drops, int64_t n_lists, int list_len,
                                             const float* __restrict__ qe2, const uint8_t* __restrict__ Q,
                                             const uint8_t* __restrict__ X, int k, int64_t row_offset,
                                             float* __restrict__ out_s, int64_t* __restrict__ out_r,
                                             Rec* __restrict__ out_rec, uint32_t* __restrict__ gate,
-                                            int* __restrict__ diag, int force, int64_t q, SelLds& sl) {
+                                            int* __restrict__ diag, int force, int64_t q, SelLdsT<CAP>& sl) {
   // U1: candidate entries per thread per round (config 3: 512 lists x 10 = 5,120 = one round, rows
   // loaded with the scores, and the drops with them: one memory round trip instead of four).
   // The exact re-score: 16 lanes per survivor row (CPL 16-B chunks of the row per lane), U rows per
@@ -110,7 +116,7 @@ __device__ __forceinline__ bool select_body(const float* __restrict__ cs, const 
     for (int u = 0; u < U1; ++u)
       if (s[u] != -__builtin_inff()) {
         const int i = atomicAdd(&sl.n_c, 1);
-        if (i < kSelCap) {
+        if (i < CAP) {
           sl.ca[i] = s[u];
           sl.crow[i] = r[u];
         }
@@ -119,14 +125,14 @@ __device__ __forceinline__ bool select_body(const float* __restrict__ cs, const 
   __syncthreads();
   RFX_SEL_T(1)
   const int nc = sl.n_c;
-  if (nc > kSelCap || force) sl.fail = 1;
-  const int ncl = nc < kSelCap ? nc : kSelCap;
+  if (nc > CAP || force) sl.fail = 1;
+  const int ncl = nc < CAP ? nc : CAP;
   // 2. a_k = the k-th best A (with multiplicity): the value v with #{> v} < k <= #{>= v}.  Every
   // candidate counts the others with 16-B broadcast reads (4 per read; the tail padded with -inf,
   // which counts for nothing).  Measured faster than extracting each wave's k best by k rounds of a
   // DPP wave max (1.96 against 4.72 us at the 8-GPU shard, ~108 candidates per query: those rounds
   // are a serial dependency chain).
-  if (tid < 3 && ncl + tid < kSelCap) sl.ca[ncl + tid] = -__builtin_inff();
+  if (tid < 3 && ncl + tid < CAP) sl.ca[ncl + tid] = -__builtin_inff();
   __syncthreads();
   {
     const float4* ca4 = (const float4*)sl.ca;

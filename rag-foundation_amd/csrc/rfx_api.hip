@@ -447,7 +447,9 @@ int grow(Index& ix, int64_t need, hipStream_t st) {
 // ---- search workspace layout ------------------------------------------------------------------
 struct SearchLayout {
   int kernel;        // 0 VALU (nq <= 8); 1 MFMA 128×BN (nq <= 64); 2 MFMA 256×256; 3 query-stationary MFMA;
-                     // 6 config-3 kernel (d 768); 7 / 8 d-1024 kernels (config 4); 9 f32 stores
+                     // 6 config-3 kernel (d 768); 7 / 8 d-1024 kernels (config 4); 9 f32 stores;
+                     // 10 the two-pass scan (k <= 10); 12 its wide form (nq >= 9, k 11..64; fbk 1 / 2 / 3, or 0 = the
+                     // VALU plan vp)
   rfx::ValuPlan vp;
   rfx::MfmaPlan mp;
   int64_t n_cand;    // candidates per query
@@ -486,7 +488,20 @@ int make_layout(const Index& ix, int64_t nq, int k, SearchLayout& L, bool search
   // for nq > 64, the 2-wave one for 9..64), whose gated fallback is the exact scan planned here: kernel 6
   // (bf16 / f16, d 768), 8 (d 1024) or 9 (f32, d 768) whatever nq, padded to their query groups.
   const bool two_pass = search && ix.screen && ix.rows > 0 && k <= 10 && rfx::screen_supported(ix.dim, ix.dtype);
-  if (nq > 8) {
+  // k 11..64 with an int8 copy: the wide form of the two-pass scan (plan 12), whose gated exact
+  // pass is the exact plan the same search has without the copy: kernels 1 / 2 / 3 at k <= 16 (planned below as
+  // ever), the VALU scan at K slot 64 above (and wherever no MFMA kernel plans, f32 stores).  Not planned (the
+  // exact plans, as before) when the default plan is not ok: fewer than 64 lists, a cell the wide form does not
+  // serve (plan_scan_screen), RFX_SCREEN_WIDE=0.  The default plan decides, so that the plan and every offset are
+  // the same whatever scan_blocks a search passes; a scan_blocks that cannot plan the wide form is ignored.
+  rfx::MfmaPlan wsp{}, wsmax{};
+  if (search && ix.screen && ix.rows > 0 && nq > 8 && k > 10 && L.vp.ok && rfx::screen_supported(ix.dim, ix.dtype)) {
+    wsmax = rfx::plan_scan_screen(ix.rows, ix.dim, ix.dtype, nq, k, 0);
+    wsp = scan_blocks ? rfx::plan_scan_screen(ix.rows, ix.dim, ix.dtype, nq, k, scan_blocks) : wsmax;
+    if (!wsp.ok) wsp = wsmax;
+  }
+  const bool wide = wsmax.ok;
+  if (nq > 8 && !(wide && k > 16)) {
     if (nq > 128 || (two_pass && nq > 8)) {
       L.mp = rfx::plan_scan_mfma6(ix.rows, ix.dim, ix.dtype, nq, k);
       if (L.mp.ok) L.kernel = 6;
@@ -545,15 +560,15 @@ int make_layout(const Index& ix, int64_t nq, int k, SearchLayout& L, bool search
   L.cr_off = L.cs_off + align_up((size_t)nq * rec_cand * 4);
   L.total = L.cr_off + align_up((size_t)nq * rec_cand * 4);
   L.fbk = 0;
-  if (search && ix.screen && ix.rows > 0 && (L.kernel == 6 || L.kernel == 8 || L.kernel == 9)) {
-    L.sp = rfx::plan_scan_screen(ix.rows, ix.dim, ix.dtype, nq, k, scan_blocks);
+  if (search && ix.screen && ix.rows > 0 && (L.kernel == 6 || L.kernel == 8 || L.kernel == 9 || wide)) {
+    L.sp = wide ? wsp : rfx::plan_scan_screen(ix.rows, ix.dim, ix.dtype, nq, k, scan_blocks);
     // the regions are sized (and placed) by the default plan, the most workgroups and lists any
     // scan_blocks gives: every offset, the gate and diag words included, is then the same whatever
     // scan_blocks a search used (rfx_screen_diag and rfx_search_plan build the default layout)
-    const rfx::MfmaPlan smax = scan_blocks ? rfx::plan_scan_screen(ix.rows, ix.dim, ix.dtype, nq, k, 0) : L.sp;
+    const rfx::MfmaPlan smax = wide ? wsmax : scan_blocks ? rfx::plan_scan_screen(ix.rows, ix.dim, ix.dtype, nq, k, 0) : L.sp;
     if (L.sp.ok && smax.ok) {
       L.fbk = L.kernel;
-      L.kernel = 10;
+      L.kernel = wide ? 12 : 10;
       const size_t nc = (size_t)std::max(L.sp.n_lists, smax.n_lists) * std::max(L.sp.k_lane, smax.k_lane);
       L.s_tau = L.total;
       L.s_cs = L.s_tau + align_up(std::max(rfx::tau_bytes_screen(L.sp), rfx::tau_bytes_screen(smax)));
@@ -686,6 +701,7 @@ int screen_search(Index& ix, const SearchLayout& L, const void* queries, int64_t
   uint32_t* gate = (uint32_t*)(ws + L.s_gate);
   int* diag = (int*)(ws + L.s_diag);
   uint32_t* tau = (uint32_t*)(ws + L.tau_off);
+  const bool wide = L.kernel == 12;
   // the fallback's threshold table ([its nq_pad][16]) is zeroed by the query quantiser: no memset launch
   if (stages & 1) {
     rfx::ScreenSeed sd;
@@ -693,12 +709,14 @@ int screen_search(Index& ix, const SearchLayout& L, const void* queries, int64_t
     sd.tmeta = ix.smeta;
     sd.nrows = (int)ix.rows;
     sd.mask = mask;
-    sd.kl = L.sp.k_lane;
-    rfx::launch_screen_queries(queries, ix.dtype, ix.dim, nq, L.sp.nq_pad, qc, qe2, ix.sstats, stau, gate, tau,
-                               L.mp.nq_pad, st, &sd);
+    // (the seed is the kl-th best of its sample rows: the list length where that is >= k, else k itself)
+    sd.kl = wide ? k : L.sp.k_lane;
+    // (the wide form's exact passes clear their own bounds: the widen launch, kernel 2 / 3's memset)
+    rfx::launch_screen_queries(queries, ix.dtype, ix.dim, nq, L.sp.nq_pad, qc, qe2, ix.sstats, stau, gate,
+                               wide ? nullptr : tau, wide ? 0 : L.mp.nq_pad, st, &sd);
     if (ev0) RFX_HIP(hipEventRecord((hipEvent_t)ev0, st));
     if (rfx::launch_scan_screen(L.sp, ix.scodes, ix.smeta, ix.sstats, (int)ix.rows, ix.dim, qc, qe2, (int)nq, stau, scs,
-                                scr, drops, st, mask) != 0)
+                                scr, drops, st, mask, k) != 0)
       return fail(RFX_EUNSUPPORTED, "screen scan launch rejected");
     if (ev1) RFX_HIP(hipEventRecord((hipEvent_t)ev1, st));
   }
@@ -709,17 +727,40 @@ int screen_search(Index& ix, const SearchLayout& L, const void* queries, int64_t
   // the select and the gated exact pass read the queries with 16-B loads: an unaligned batch (or one
   // that is not a whole number of the fallback's query groups) is copied once into the workspace
   const void* qpad = queries;
-  if (nq != L.mp.nq_pad || ((uintptr_t)queries & 15)) {
+  const bool valu_fb = wide && L.fbk == 0;
+  if (valu_fb ? ((uintptr_t)queries & 15) != 0 : (nq != L.mp.nq_pad || ((uintptr_t)queries & 15))) {
+    // (VALU exact pass: the select reads nq queries; the copy shares q_off with the exact pass's f32 queries,
+    // which the widen launch writes after the select on the same stream)
     qpad = ws + L.q_off;
-    rfx::launch_pad_queries(queries, nq, L.mp.nq_pad, ix.dim, esize(ix.dtype), (void*)qpad, st);
+    rfx::launch_pad_queries(queries, nq, valu_fb ? nq : L.mp.nq_pad, ix.dim, esize(ix.dtype), (void*)qpad, st);
   }
   float* cs = (float*)(ws + L.cs_off);
   int32_t* cr = (int32_t*)(ws + L.cr_off);
   if (rfx::launch_screen_select(scs, scr, drops, L.sp.n_lists, L.sp.k_lane, qe2, qpad, ix.data, ix.dim, ix.dtype, nq,
                                 k, row_offset, out_s, out_r, out_rec, gate, diag, ix.screen == 2, st) != 0)
     return fail(RFX_EUNSUPPORTED, "screen select k=%d unsupported", k);
+  const rfx::Rescore rs{ix.data, queries, ix.dim, ix.dtype, ix.rows};
+  if (valu_fb) {
+    // gated exact pass of the wide form at k > 16: the VALU scan (K slot 64) and its merge, both on the gate word;
+    // the query widening (nq x dim, which also zeroes the scan's bounds) runs ungated
+    float* qf = (float*)(ws + L.q_off);
+    rfx::launch_widen_queries(queries, nq * ix.dim, ix.dtype, qf, st, tau, nq);
+    if (rfx::launch_scan_valu(L.vp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qf, (int)nq, cs, cr, st, mask, tau, gate) != 0)
+      return fail(RFX_EUNSUPPORTED, "fallback VALU scan launch rejected");
+    if (rfx::launch_topk_merge_lists(cs, cr, 0, nq, L.n_cand, L.vp.k_slot, k, row_offset, out_rec ? nullptr : out_s,
+                                     out_rec ? nullptr : out_r, out_rec, st, /*sorted=*/true, gate, &rs) != 0)
+      return fail(RFX_EUNSUPPORTED, "merge k=%d unsupported", k);
+    RFX_HIP(hipGetLastError());
+    return RFX_OK;
+  }
   // gated exact pass (no work unless the select kernel set the gate)
-  const int rc = L.fbk == 6 ? rfx::launch_scan_mfma6(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs,
+  const int rc = L.fbk == 1 ? rfx::launch_scan_mfma(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, cs, cr, st,
+                                                    mask, gate)
+                 : L.fbk == 2 ? rfx::launch_scan_mfma2(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs,
+                                                       cr, st, mask, gate)
+                 : L.fbk == 3 ? rfx::launch_scan_mfma3(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs,
+                                                       cr, st, mask, gate)
+                 : L.fbk == 6 ? rfx::launch_scan_mfma6(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs,
                                                      cr, st, mask, gate, true)
                  : L.fbk == 8 ? rfx::launch_scan_mfma8(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs,
                                                        cr, st, mask, gate, true)
@@ -727,7 +768,6 @@ int screen_search(Index& ix, const SearchLayout& L, const void* queries, int64_t
                                                        cr, st, mask, gate, true);
   if (rc != 0) return fail(RFX_EUNSUPPORTED, "fallback scan launch rejected (%d)", rc);
   // (the fallback's final top-k re-scored by the two-pass rule: the same bits as the select's answer)
-  const rfx::Rescore rs{ix.data, queries, ix.dim, ix.dtype, ix.rows};
   if (rfx::launch_topk_merge_lists(cs, cr, 0, nq, L.n_cand, L.mp.k_lane, k, row_offset, out_rec ? nullptr : out_s,
                                    out_rec ? nullptr : out_r, out_rec, st, /*sorted=*/true, gate, &rs) != 0)
     return fail(RFX_EUNSUPPORTED, "merge k=%d unsupported", k);
@@ -1729,7 +1769,7 @@ int search_impl(rfx_index_t h, const void* queries_d, int64_t nq, int k, const u
     if (ev) RFX_HIP(hipEventRecord((hipEvent_t)ev, st));
     return RFX_OK;
   };
-  if (L.kernel == 10)
+  if (L.kernel == 10 || L.kernel == 12)
     return screen_search(*ix, L, queries_d, nq, k, row_mask_d, row_offset, out_scores_d, out_rows_d, out_rec, ws, st,
                          ev0, ev1, stages);
   if (!(stages & 1)) return RFX_OK;  // another plan: the whole search is stage 1
@@ -2140,7 +2180,8 @@ int rfx_screen_diag(rfx_index_t h, int64_t nq, int k, const void* ws_d, int32_t*
   SearchLayout L;
   int rc = make_search_layout(*ix, nq, k, L);
   if (rc) return rc;
-  if (L.kernel != 10) return fail(RFX_EINVAL, "the search plan for nq=%lld k=%d is not the two-pass scan", (long long)nq, k);
+  if (L.kernel != 10 && L.kernel != 12)
+    return fail(RFX_EINVAL, "the search plan for nq=%lld k=%d is not the two-pass scan", (long long)nq, k);
   RFX_HIP(hipSetDevice(ix->device));
   if (diag_h && nq) RFX_HIP(hipMemcpy(diag_h, (const uint8_t*)ws_d + L.s_diag, (size_t)nq * 8, hipMemcpyDeviceToHost));
   if (fallback_h) RFX_HIP(hipMemcpy(fallback_h, (const uint8_t*)ws_d + L.s_gate, 4, hipMemcpyDeviceToHost));

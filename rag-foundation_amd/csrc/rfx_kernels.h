@@ -38,9 +38,11 @@ ValuPlan plan_scan_valu(int64_t nrows, int D, int dtype, int64_t nq, int k);
 // mask (every scan launcher): optional row mask, bit (r & 31) of word r >> 5 set = row r may be
 // returned, (nrows + 31) / 32 words; nullptr = all rows (the production kernels run unchanged).
 // tau: optional [nq] u32 pruning bounds, zeroed beforehand (launch_widen_queries)
+// gate (optional): a device word; the launch returns at once when it is clear (the exact pass of the wide
+// two-pass scan, plan 12)
 int launch_scan_valu(const ValuPlan& p, const void* X, int nrows, int D, int dtype, const float* Qf,
                      int nq, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr,
-                     uint32_t* tau = nullptr);
+                     uint32_t* tau = nullptr, const uint32_t* gate = nullptr);
 // The whole search (scan + final merge) in one launch for a VALU plan with nq <= kValuFusedMaxNq:
 // Q is the raw [nq][D] query buffer in the index dtype; state = kValuFusedMaxNq bounds followed by
 // p.q_slices arrival counters, ALL ZERO on entry — the kernel leaves them zero again, so a state
@@ -88,18 +90,23 @@ struct MfmaPlan {
   bool ok;
 };
 MfmaPlan plan_scan_mfma(int64_t nrows, int D, int dtype, int64_t nq, int k);
+// gate (kernels 1, 2, 3; optional): a device word; the kernel returns at once when it is clear (the exact pass of
+// the wide two-pass scan at k 11..16, plan 12).  Kernels 2 / 3 clear their bounds by a memset either way.
 int launch_scan_mfma(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad,
-                     int nq, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr);
+                     int nq, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr,
+                     const uint32_t* gate = nullptr);
 int launch_scan_mfma_dbg(const MfmaPlan& p, int mode, const void* X, int nrows, int D, const void* Qpad, int nq,
                          float* cs, int* cr, hipStream_t st);
 MfmaPlan plan_scan_mfma2(int64_t nrows, int D, int dtype, int64_t nq, int k);
 int launch_scan_mfma2(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr);
+                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr,
+                      const uint32_t* gate = nullptr);
 int launch_scan_mfma2_dbg(const MfmaPlan& p, int mode, const void* X, int nrows, int D, const void* Qpad, int nq,
                           uint32_t* tau, float* cs, int* cr, hipStream_t st);
 MfmaPlan plan_scan_mfma3(int64_t nrows, int D, int dtype, int64_t nq, int k);
 int launch_scan_mfma3(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr);
+                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr,
+                      const uint32_t* gate = nullptr);
 size_t tau_bytes_mfma6(const MfmaPlan& p);
 MfmaPlan plan_scan_mfma6(int64_t nrows, int D, int dtype, int64_t nq, int k);
 // gate (optional): a device word; the launch does nothing unless it is non-zero (the exact pass of
@@ -156,7 +163,10 @@ bool screen_supported(int D, int dtype);
 // tmeta: per tile 16 B {f32 scale, u32 live word, 0, 0}
 void launch_screen_quantize(const void* X, int D, int dtype, int64_t tile0, int64_t ntiles, const int64_t* tiles_d,
                             int8_t* codes, void* tmeta, uint32_t* stats, hipStream_t st);
+// k <= 10: kernel 10 (lists of 4 / 10).  k 11..64 with nq >= 9: its wide form (lists of 16, plan 12; not ok
+// with RFX_SCREEN_WIDE=0 or fewer than 64 lists)
 MfmaPlan plan_scan_screen(int64_t nrows, int D, int dtype, int64_t nq, int k, int max_blocks = 0);
+bool screen_wide_enabled();
 size_t tau_bytes_screen(const MfmaPlan& p);
 uint32_t* xcd_weights_device_ptr();  // kernel 10's per-device XCD weight table (k_screen.hip g_xcd_w)
 // ftau (or null): the gated fallback scan's threshold table ([nq_pad][kFallbackTauW], kernel 6 / 8),
@@ -177,7 +187,7 @@ void launch_screen_queries(const void* Q, int dtype, int D, int64_t nq, int64_t 
                            hipStream_t st, const ScreenSeed* sd = nullptr);
 int launch_scan_screen(const MfmaPlan& p, const int8_t* codes, const void* tmeta, const uint32_t* stats, int nrows, int D,
                        const int8_t* Qc, const float* qe2, int nq, uint32_t* tau, float* cs, int* cr, uint32_t* drops,
-                       hipStream_t st, const uint32_t* mask);
+                       hipStream_t st, const uint32_t* mask, int k = 0);  // k: the requested top-k (the wide form)
 int launch_screen_select(const float* cs, const int* cr, const uint32_t* drops, int64_t n_lists, int list_len,
                          const float* qe2, const void* Q, const void* X, int D, int dtype, int64_t nq, int k,
                          int64_t row_offset, float* out_s, int64_t* out_r, void* out_rec, uint32_t* gate, int* diag,

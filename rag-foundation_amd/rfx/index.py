@@ -430,7 +430,8 @@ class DeviceIndex:
 
     def search_plan(self, nq: int, k: int) -> int:
         """Kernel rfx_search runs for (nq, k): 10 = the two-pass scan of a batch (int8 MFMA screen),
-        11 = the two-pass scan of up to 8 questions (int8 dot4 screen, one launch)."""
+        11 = the two-pass scan of up to 8 questions (int8 dot4 screen, one launch), 12 = the wide form of
+        kernel 10 (9 or more questions at k 11..64)."""
         kern = ctypes.c_int()
         check(lib.rfx_search_plan(self.handle, int(nq), int(k), ctypes.byref(kern)))
         return kern.value
