@@ -1,0 +1,303 @@
+// k_deep.hip — the deep search kernels (k_deep.h): scan with threshold + LDS buffer + periodic sort, and the
+// per-question merge with the f64 re-score.  gfx950 only.
+#include "k_deep.h"
+
+#include "k_mfma_common.h"
+#include "k_scan_valu.h"  // elem_rt: the score rule's element widening
+
+namespace rfx {
+namespace {
+
+using mfc::v4f32x4;
+
+constexpr int kDeepQSlots = 16;  // threshold / count slots of a workgroup (questions per workgroup <= 16)
+
+// (score desc, row asc) as one unsigned order; s + 0 folds -0 into +0, which compare equal as floats
+__device__ __forceinline__ uint64_t deep_key(float s, int row) {
+  return ((uint64_t)ord_f32(s + 0.0f) << 32) | (uint32_t)~(uint32_t)row;
+}
+__device__ __forceinline__ float deep_key_score(uint64_t key) { return mfc::unord((uint32_t)(key >> 32)); }
+__device__ __forceinline__ int deep_key_row(uint64_t key) { return (int)~(uint32_t)key; }
+
+// LDS of a workgroup: nqg buffers of 2 * KB keys, then the thresholds (keys; 0 = none yet) and the fills.
+struct DeepBuf {
+  uint64_t* buf;
+  uint64_t* tau;
+  int* cnt;
+  int KB;
+  __device__ __forceinline__ DeepBuf(uint64_t* lds, int nqg, int kb)
+      : buf(lds), tau(lds + (size_t)nqg * 2 * kb), cnt((int*)(lds + (size_t)nqg * 2 * kb + kDeepQSlots)), KB(kb) {}
+};
+size_t deep_lds_bytes(int nqg, int kb) { return (size_t)nqg * 2 * kb * 8 + kDeepQSlots * 8 + kDeepQSlots * 4; }
+
+// Wave-wide (every lane calls it).  The passing lanes among `mine` (the lanes that hold this lane's question, itself
+// included) claim consecutive slots of the question's buffer: one ballot, a prefix count, one LDS add by the first
+// of them.  Returns the lane's slot, or -1.
+__device__ __forceinline__ int deep_claim(bool pass, uint64_t mine, int* cnt_q) {
+  const int lane = lane_id();
+  const uint64_t m = __ballot(pass) & mine;
+  const int leader = m ? __builtin_ctzll(m) : lane;
+  int base = 0;
+  if (pass && lane == leader) base = atomicAdd(cnt_q, __popcll(m));
+  base = __shfl(base, leader);
+  return pass ? base + __popcll(m & ((1ull << lane) - 1)) : -1;
+}
+
+// Workgroup-wide: the buffers named in `need` (uniform), n keys each (a power of two, `stride` keys apart),
+// sorted best first.  Bitonic, in place; ends on a barrier.
+__device__ __forceinline__ void deep_sort(uint64_t* buf, int stride, uint32_t need, int n) {
+  for (int k2 = 2; k2 <= n; k2 <<= 1)
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      for (uint32_t m = need; m; m &= m - 1) {
+        uint64_t* b = buf + (size_t)__builtin_ctz(m) * stride;
+        for (int i = threadIdx.x; i < n / 2; i += blockDim.x) {
+          const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
+          const uint64_t a = b[lo], c = b[hi];
+          if ((a < c) == ((lo & k2) == 0)) {
+            b[lo] = c;
+            b[hi] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+}
+
+// Workgroup-wide meeting after a round of appends.  Every buffer that holds more than `lim` keys is sorted, its
+// KB best stay and the KB-th becomes its threshold (lim = -1: every buffer, the final cut).  Returns the buffers
+// it cut (uniform).  Nothing may be appended between the entry and the return.
+__device__ __forceinline__ uint32_t deep_compact(const DeepBuf& B, int nqg, int lim) {
+  const int N = 2 * B.KB;
+  __syncthreads();  // the round's appends are in
+  uint32_t need = 0;
+  for (int q = 0; q < nqg; ++q) need |= (B.cnt[q] > lim ? 1u : 0u) << q;
+  __syncthreads();  // every thread has read the fills before anyone appends again
+  if (!need) return 0;
+  for (uint32_t m = need; m; m &= m - 1) {
+    const int q = __builtin_ctz(m);
+    for (int i = min(B.cnt[q], N) + (int)threadIdx.x; i < N; i += blockDim.x) B.buf[(size_t)q * N + i] = 0;
+  }
+  __syncthreads();
+  deep_sort(B.buf, N, need, N);
+  if ((int)threadIdx.x < nqg && ((need >> threadIdx.x) & 1u)) {
+    B.cnt[threadIdx.x] = min(B.cnt[threadIdx.x], B.KB);
+    B.tau[threadIdx.x] = B.buf[(size_t)threadIdx.x * N + B.KB - 1];
+  }
+  __syncthreads();
+  return need;
+}
+
+// ---- scan ---------------------------------------------------------------------------------------------------
+// A fragments of the 16-row tile at r0 (NDS * 64 columns at most, nds * 64 in use) and the tile's live bits:
+// bit i set = row r0 + i is inside the range and selected by the mask.  A tile past the range loads nothing.
+template <int NDS>
+__device__ __forceinline__ void deep_load_tile(uint4 (&a)[2 * NDS], uint32_t& bits, const uint8_t* __restrict__ X, int D,
+                                               int nds, int r0, int r_hi, const uint32_t* __restrict__ mask, int n,
+                                               int g) {
+  bits = 0;
+  if (r0 >= r_hi) return;
+  const int left = r_hi - r0;
+  uint32_t w = mask ? mask[r0 >> 5] >> (r0 & 31) : 0xffffu;
+  w &= 0xffffu;
+  if (left < 16) w &= (1u << left) - 1u;
+  bits = w;
+  const int row = min(r0 + n, r_hi - 1);  // a row past the range: any row of it (its bit is clear)
+  const mfc::v4i32* src = (const mfc::v4i32*)(X + (int64_t)row * D * 2 + g * 32);  // read once: non-temporal
+#pragma unroll
+  for (int ds = 0; ds < NDS; ++ds)
+    if (ds < nds) {
+      a[2 * ds] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(src + ds * 8));
+      a[2 * ds + 1] = __builtin_bit_cast(uint4, __builtin_nontemporal_load(src + ds * 8 + 1));
+    }
+}
+
+// One tile against the resident questions: 2 * nds MFMAs, one compare per accumulator register, one ballot.
+template <int DT, int NDS>
+__device__ __forceinline__ void deep_use_tile(const uint4 (&a)[2 * NDS], uint32_t bits, const uint4 (&bq)[2 * NDS], int nds,
+                                              float thr, int r0, int n, int g, const DeepBuf& B) {
+  if (!bits) return;  // (wave-uniform)
+  v4f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int ds = 0; ds < NDS; ++ds)
+    if (ds < nds) {
+      acc0 = mfc::mfma16<DT>(a[2 * ds], bq[2 * ds], acc0);
+      acc1 = mfc::mfma16<DT>(a[2 * ds + 1], bq[2 * ds + 1], acc1);
+    }
+  const v4f32x4 acc = acc0 + acc1;
+  const uint32_t nb = bits >> (4 * g);
+  bool p[4];
+  bool any = false;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    p[i] = acc[i] > thr && ((nb >> i) & 1u);  // NaN (a tombstoned row) never passes
+    any |= p[i];
+  }
+  if (!__ballot(any)) return;
+  const int N = 2 * B.KB;
+  const uint64_t mine = 0x0001000100010001ull << n;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int slot = deep_claim(p[i], mine, &B.cnt[n]);
+    if (slot >= 0 && slot < N) B.buf[(size_t)n * N + slot] = deep_key(acc[i], r0 + 4 * g + i);
+  }
+}
+
+template <int DT, int NDS>
+__global__ __launch_bounds__(kDeepThreads) void deep_scan_kernel(const uint8_t* __restrict__ X, int nrows, int D,
+                                                                 const uint8_t* __restrict__ Q, int nq,
+                                                                 const uint32_t* __restrict__ mask, DeepPlan P,
+                                                                 uint64_t* __restrict__ ws) {
+  extern __shared__ __attribute__((aligned(16))) uint64_t deep_lds[];
+  const int QG = P.q_per_wg, KB = P.kb, N = 2 * KB;
+  const DeepBuf B(deep_lds, QG, KB);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, g = lane >> 4;
+  const int q0 = blockIdx.y * QG;
+  const bool qlive = n < QG && q0 + n < nq;
+  const int r_lo = (int)min((int64_t)blockIdx.x * P.rows_per_range, (int64_t)nrows);
+  const int r_hi = (int)blockIdx.x == P.ranges - 1 ? nrows : r_lo + P.rows_per_range;
+  const int nds = D >> 6;
+  if (tid < kDeepQSlots) {
+    B.cnt[tid] = 0;
+    B.tau[tid] = 0;
+  }
+  __syncthreads();
+
+  uint4 bq[2 * NDS];
+  {
+    const uint4* src = (const uint4*)(Q + (int64_t)(qlive ? q0 + n : 0) * D * 2 + g * 32);
+#pragma unroll
+    for (int ds = 0; ds < NDS; ++ds) {
+      bq[2 * ds] = bq[2 * ds + 1] = make_uint4(0, 0, 0, 0);
+      if (ds < nds && qlive) {
+        bq[2 * ds] = src[ds * 8];
+        bq[2 * ds + 1] = src[ds * 8 + 1];
+      }
+    }
+  }
+  // a lane of no question (past the group, past nq) never passes
+  float thr = qlive ? -__builtin_inff() : __builtin_inff();
+
+  const int T = (r_hi - r_lo + kDeepRound - 1) / kDeepRound;  // rounds: one tile per wave each
+  const int lim = N - P.check_rounds * kDeepRound;
+  uint4 a0[2 * NDS], a1[2 * NDS];
+  uint32_t bits0 = 0, bits1 = 0;
+  auto tile_row = [&](int t) { return r_lo + (t * 4 + wave) * 16; };
+  if (T > 0) deep_load_tile<NDS>(a0, bits0, X, D, nds, tile_row(0), r_hi, mask, n, g);
+  for (int t = 0; t < T; t += 2) {
+    if (t + 1 < T) deep_load_tile<NDS>(a1, bits1, X, D, nds, tile_row(t + 1), r_hi, mask, n, g);
+    deep_use_tile<DT, NDS>(a0, bits0, bq, nds, thr, tile_row(t), n, g, B);
+    if (t + 1 < T) {
+      if (t + 2 < T) deep_load_tile<NDS>(a0, bits0, X, D, nds, tile_row(t + 2), r_hi, mask, n, g);
+      deep_use_tile<DT, NDS>(a1, bits1, bq, nds, thr, tile_row(t + 1), n, g, B);
+    }
+    // (check_rounds is even: a meeting falls after the second tile of a pair)
+    if ((t + 2) % P.check_rounds == 0 && deep_compact(B, QG, lim) && qlive) {
+      const uint64_t tk = B.tau[n];
+      thr = tk ? deep_key_score(tk) : -__builtin_inff();
+    }
+  }
+  deep_compact(B, QG, -1);
+  for (int i = tid; i < QG * KB; i += kDeepThreads) {
+    const int q = i / KB, j = i - q * KB;
+    if (q0 + q < nq) ws[((size_t)(q0 + q) * P.ranges + blockIdx.x) * KB + j] = B.buf[(size_t)q * N + j];
+  }
+}
+
+// ---- merge --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kDeepThreads) void deep_merge_kernel(const uint64_t* __restrict__ ws, int ranges, int KB, int k,
+                                                                  const void* __restrict__ X, int nrows, int D, int dtype,
+                                                                  const void* __restrict__ Q, float* __restrict__ out_s,
+                                                                  int64_t* __restrict__ out_r) {
+  extern __shared__ __attribute__((aligned(16))) uint64_t deep_lds[];
+  const DeepBuf B(deep_lds, 1, KB);
+  const int tid = threadIdx.x, N = 2 * KB;
+  const int64_t q = blockIdx.x;
+  if (tid < kDeepQSlots) {
+    B.cnt[tid] = 0;
+    B.tau[tid] = 0;
+  }
+  __syncthreads();
+  const int total = ranges * KB, R = min(kDeepThreads, KB), lim = N - R;
+  const uint64_t* src = ws + (size_t)q * total;
+  for (int base = 0; base < total; base += R) {
+    const int i = base + tid;
+    const uint64_t key = tid < R && i < total ? src[i] : 0;
+    const bool pass = key > B.tau[0];  // the full key: equal scores of different ranges go to the lower row
+    const int slot = deep_claim(pass, ~0ull, &B.cnt[0]);
+    if (slot >= 0 && slot < N) B.buf[slot] = key;
+    deep_compact(B, 1, lim);
+  }
+  deep_compact(B, 1, -1);  // buf[0 .. KB): the best, in order; empty places (key 0) last
+
+  // the score rule of every search: fl32 of the f64 dot of the stored values (8 lanes per entry, the
+  // summation order of rescore_final), then the order again under the new scores
+  const int gl = tid & 7;
+  for (int e0 = 0; e0 < KB; e0 += kDeepThreads / 8) {
+    const int e = e0 + (tid >> 3);
+    const uint64_t key = e < k ? B.buf[e] : 0;
+    int row = key ? deep_key_row(key) : -1;
+    if (row >= nrows) row = -1;
+    double acc = 0.0;
+    if (row >= 0) {
+      const int64_t xr = (int64_t)row * D, qr = q * D;
+      for (int c = gl; c < D; c += 8) acc += (double)elem_rt(X, xr + c, dtype) * (double)elem_rt(Q, qr + c, dtype);
+    }
+#pragma unroll
+    for (int off = 4; off; off >>= 1) acc += __shfl_xor(acc, off);
+    if (gl == 0) B.buf[KB + e] = row >= 0 ? deep_key((float)acc, row) : 0;
+  }
+  __syncthreads();
+  deep_sort(B.buf + KB, KB, 1u, KB);
+  for (int j = tid; j < k; j += kDeepThreads) {
+    const uint64_t key = B.buf[KB + j];
+    out_s[q * k + j] = key ? deep_key_score(key) : -__builtin_inff();
+    out_r[q * k + j] = key ? (int64_t)deep_key_row(key) : -1;
+  }
+}
+
+template <int DT, int NDS>
+int launch_scan(const DeepPlan& p, const void* X, int nrows, int D, const void* Q, int nq, const uint32_t* mask, uint64_t* ws,
+                hipStream_t st) {
+  auto kern = deep_scan_kernel<DT, NDS>;
+  const size_t lds = deep_lds_bytes(p.q_per_wg, p.kb);
+  if (lds > (size_t)kDeepLdsBudget) return -1;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
+    return -1;
+  hipLaunchKernelGGL(kern, dim3((unsigned)p.ranges, (unsigned)p.q_groups), dim3(kDeepThreads), lds, st, (const uint8_t*)X,
+                     nrows, D, (const uint8_t*)Q, nq, mask, p, ws);
+  return 0;
+}
+
+template <int DT>
+int launch_scan_dt(const DeepPlan& p, const void* X, int nrows, int D, const void* Q, int nq, const uint32_t* mask,
+                   uint64_t* ws, hipStream_t st) {
+  switch ((D / 64 + 3) / 4) {
+    case 1: return launch_scan<DT, 4>(p, X, nrows, D, Q, nq, mask, ws, st);
+    case 2: return launch_scan<DT, 8>(p, X, nrows, D, Q, nq, mask, ws, st);
+    case 3: return launch_scan<DT, 12>(p, X, nrows, D, Q, nq, mask, ws, st);
+    case 4: return launch_scan<DT, 16>(p, X, nrows, D, Q, nq, mask, ws, st);
+  }
+  return -1;
+}
+
+}  // namespace
+
+int launch_deep_search(const DeepPlan& p, const void* X, int64_t nrows, int D, int dtype, const void* Q, int64_t nq, int k,
+                       const uint32_t* mask, uint64_t* ws, float* out_s, int64_t* out_r, hipStream_t st) {
+  if (dtype != RFX_BF16 && dtype != RFX_F16) return -1;
+  if (D < 64 || D > kDeepMaxDim || D % 64 != 0) return -1;
+  if (nq < 1 || nq > kDeepMaxNq || k < kDeepMinK || k > p.kb || nrows < 0 || nrows > 0x7fffffffll - 1) return -1;
+  if (p.ranges < 1 || p.check_rounds < 2 || p.check_rounds % 2 != 0 || 2 * p.kb < p.kb + p.check_rounds * kDeepRound ||
+      p.q_per_wg > kDeepQSlots || (int64_t)(p.ranges - 1) * p.rows_per_range > nrows)
+    return -1;
+  const int rc = dtype == RFX_BF16 ? launch_scan_dt<RFX_BF16>(p, X, (int)nrows, D, Q, (int)nq, mask, ws, st)
+                                   : launch_scan_dt<RFX_F16>(p, X, (int)nrows, D, Q, (int)nq, mask, ws, st);
+  if (rc) return rc;
+  const size_t lds = deep_lds_bytes(1, p.kb);
+  hipLaunchKernelGGL(deep_merge_kernel, dim3((unsigned)nq), dim3(kDeepThreads), lds, st, ws, p.ranges, p.kb, k, X, (int)nrows,
+                     D, dtype, Q, out_s, out_r);
+  return 0;
+}
+
+}  // namespace rfx

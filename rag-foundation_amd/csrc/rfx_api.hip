@@ -33,6 +33,7 @@
 #include <string>
 #include <vector>
 
+#include "index_access.h"
 #include "k_compact.h"
 #include "k_mmr.h"
 #include "k_distinct.h"
@@ -834,6 +835,17 @@ int api_fail(int code, const char* fmt, ...) {
   va_end(ap);
   g_err = buf;
   return code;
+}
+
+int api_index_read(rfx_index_t h, IndexRead* out) {
+  auto ix = get(h);
+  if (!ix) return fail(RFX_EINVAL, "unknown index handle");
+  RFX_RLOCK(ix);
+  out->lk = std::move(lk);
+  out->device = ix->device, out->dim = ix->dim, out->dtype = ix->dtype;
+  out->rows = ix->rows, out->data = ix->data, out->view = ix->view;
+  out->keep = ix;
+  return RFX_OK;
 }
 }  // namespace rfx
 

@@ -159,9 +159,11 @@ class LocalGpuRag:
     # -------- Query (sync & stream) --------
     def retrieve(self, question: str, store_names: Sequence[str], k: Optional[int] = None,
                  metadata_filter: Optional[Any] = None, diversity: Optional[Any] = None,
-                 hybrid: Optional[Any] = None, distinct: Optional[Any] = None):
+                 hybrid: Optional[Any] = None, distinct: Optional[Any] = None, top_k: Optional[int] = None):
         """Top-k hits.  k: the request's top_k (the reference route drops it,
-        chat.py:66), default self.top_k; 1..64.  diversity: a lambda in [0, 1] or {"lambda": ..,
+        chat.py:66), default self.top_k; 1..64.  top_k (keyword; in place of k): 1..1024 — above 64 the hits are
+        GpuRetriever.candidates' (the deep search: flat bf16 / f16 stores, no diversity, hybrid or distinct;
+        what a re-ranking stage reads), up to 64 the same as k.  diversity: a lambda in [0, 1] or {"lambda": ..,
         "fetch_k": ..} picks the k hits by MMR from the fetch_k best (GpuRetriever.search); None = the
         default of RFX_MMR_LAMBDA (unset: off).  hybrid: an alpha in [0, 1] or {"alpha", "fetch_k", "rrf_c",
         "k1", "b"} fuses the dense answer with the BM25 answer over the chunk texts (GpuRetriever.search;
@@ -170,6 +172,10 @@ class LocalGpuRag:
         files (GpuRetriever.search; ValueError on a sharded or IVF store and together with diversity or hybrid);
         False = off; None = the default of RFX_DISTINCT (unset: off)."""
         filt = metadata_filter if self.apply_filters else None
+        if top_k is not None:
+            if int(top_k) > 64:
+                return self.retriever.candidates(list(store_names or []), question, int(top_k), metadata_filter=filt)
+            k = int(top_k)
         div = self.diversity if diversity is None else diversity
         hyb = self.hybrid if hybrid is None else hybrid
         dst = self.distinct if distinct is None else distinct

@@ -213,6 +213,29 @@ class DeviceIndex:
                                             ptr(ws), ws.numel(), stream_ptr(stream)))
         return out_s, out_r
 
+    def deep_workspace_bytes(self, nq: int, k: int) -> int:
+        b = ctypes.c_size_t()
+        check(lib.rfx_search_deep_workspace_bytes(self.handle, int(nq), int(k), ctypes.byref(b)))
+        return b.value
+
+    def search_deep(self, queries: torch.Tensor, k: int, row_mask: torch.Tensor = None, workspace: torch.Tensor = None,
+                    stream=None):
+        """Exact top-k rows per query for k in 65..1024 on a bf16 / f16 store (rfx_search_deep): (scores f32
+        [nq][k], rows int64 [nq][k]) on the device, padded with (-inf, -1) past the selected live rows."""
+        q = self._check_queries(queries)
+        nq = q.shape[0]
+        dev = q.device
+        need = self.deep_workspace_bytes(nq, k)
+        out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        ws = workspace if workspace is not None and workspace.numel() >= need else \
+            torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        m, _ = self._check_mask(row_mask, dev)
+        with torch.cuda.device(dev):
+            check(lib.rfx_search_deep(self.handle, ptr(q), nq, int(k), ptr(m) if m is not None else None, ptr(out_s),
+                                      ptr(out_r), ptr(ws), ws.numel(), stream_ptr(stream)))
+        return out_s, out_r
+
     def search_segmented(self, queries: torch.Tensor, k: int, groups, workspace: torch.Tensor = None, stream=None):
         """One launch for questions under different metadata filters (rfx_search_segmented): `groups` is a
         list of (query_indices, [(first, count), ...]); a query is answered over its group's row ranges only
@@ -566,6 +589,13 @@ def compact_plan(rows: int, ranges):
                                chunks.ctypes.data if chunks.size else None, n.value, ctypes.byref(kept),
                                ctypes.byref(n)))
     return kept.value, table, chunks
+
+
+def deep_plan(rows: int, dim: int, dtype: str, nq: int, k: int):
+    """Host only (rfx_deep_plan): (row ranges, rows per range, KB, questions per workgroup) of a deep search."""
+    out = (ctypes.c_int * 4)()
+    check(lib.rfx_deep_plan(int(rows), int(dim), _lib.DTYPE_CODES[dtype], int(nq), int(k), out))
+    return tuple(out)
 
 
 def _check_cands(cand_s: torch.Tensor, cand_r: torch.Tensor):

@@ -175,6 +175,15 @@ def _search_diverse(index, q, items, div_at, row_mask=None):
     return s.cpu(), r.cpu()
 
 
+DEEP_ERROR = "candidates beyond 64 need flat bf16 / f16 single-device stores"
+
+
+def _deep_ok(st) -> bool:
+    """A flat bf16 / f16 store on one device: its index runs the deep search (DeviceIndex.search_deep)."""
+    return hasattr(st.index, "search_deep") and getattr(st, "spec", {}).get("kind", "flat") == "flat" and \
+        st.dtype in ("bf16", "f16")
+
+
 class _StoreAnswer(tuple):
     """(store, scores, rows) of one question, plus .generation: the store generation whose row numbering
     `rows` uses (LocalStore.row_info translates or refuses rows of an earlier one after a compaction)."""
@@ -820,6 +829,51 @@ class GpuRetriever:
             st, s, r = res
             gen = getattr(res, "generation", None)
             for sc, row in zip(s, r):
+                info = st.row_info(row, gen) if row >= 0 else None
+                if info is None:
+                    continue
+                fid, text, title, uri = info
+                hits.append((-sc, si, row, Hit(sc, name, row, fid, text, title, uri)))
+        hits.sort(key=lambda h: h[:3])
+        return [h[3] for h in hits[:k]]
+
+    def candidates(self, store_names, question, k, metadata_filter=None):
+        """The k best hits for 1 <= k <= 1024, rank order (score desc, store order, row asc): the candidate
+        set of a stage behind the retriever (re-ranking, rank fusion, recall@100).  Up to 64 it is search();
+        above, each named store answers with the deep search (DeviceIndex.search_deep, exact) under its own
+        lock and row numbering, and the answers are merged.  ValueError (DEEP_ERROR) on a sharded, IVF or f32
+        store."""
+        k = int(k)
+        if not 1 <= k <= 1024:
+            raise ValueError(f"k={k} out of range [1, 1024]")
+        if k <= 64:
+            return self.search(store_names, question, k, metadata_filter)
+        filt = filters.check_filter(metadata_filter)
+        names = list(dict.fromkeys(store_names or []))
+        self.last_path = "per-store"
+        hits = []
+        for si, name in enumerate(names):
+            st = self.registry.get(name)
+            if st is None:
+                continue
+            if not _deep_ok(st):
+                raise ValueError(DEEP_ERROR)
+            if st.index.rows == 0:
+                continue
+
+            def run(st=st):
+                mask = st.row_mask(filt) if filt is not None else None
+                if filt is not None and mask is None:
+                    return None
+                with torch.cuda.device(st.device), st.lock:  # no append moves the rows under the scan
+                    q = self.embedder(st.dim).embed_texts([question], st.dtype)
+                    s, r = st.index.search_deep(q, k, row_mask=mask)
+                    return s[0].cpu().tolist(), r[0].cpu().tolist()
+
+            res, gen = _numbered(st, run)
+            if res is None:
+                continue
+            for sc, row in zip(*res):
                 info = st.row_info(row, gen) if row >= 0 else None
                 if info is None:
                     continue
