@@ -571,6 +571,29 @@ int rfx_rerank_candidates(const void* queries_d, int64_t nq, int dtype, const vo
                           int rows_dtype, int64_t row_lo, int64_t n_rows, int dim,
                           const int64_t* cand_d, int n_cand, float* out_scores_d,
                           int64_t* out_rows_d, void* stream);
+/* Deep search through the posting lists: the top-k of the probed lists' rows for k in 65..1,024
+ * (else RFX_EINVAL), the numerics and the ranking rule of rfx_ivf_search.  Every probed row's score is written
+ * once as a u64 key into a per-question slab, then one workgroup per question selects its k best (radix passes,
+ * one LDS sort).  A score of -0.0 is reported as +0.0.  row_mask_d: NULL, or the row bitmap of
+ * rfx_ivf_search_masked (mask_words its length).  Outputs [nq][k], padded (-inf, -1).  ws_d: 16-byte aligned.
+ * The slab stride is the row count of the nprobe longest lists, recorded at every list build.  On an index with
+ * rows added since its last build, the workspace call answers a bound (those lists plus the added rows; every
+ * row after a re-training), never less than the search, which builds first, needs: rfx_ivf_build before the
+ * workspace call gives the exact size. */
+int rfx_ivf_search_deep_workspace_bytes(rfx_ivf_t h, int64_t nq, int k, int nprobe, size_t* out_bytes);
+int rfx_ivf_search_deep(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe,
+                        const uint32_t* row_mask_d, int64_t mask_words, float* out_scores_d,
+                        int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream);
+/* The same with the exact re-rank: the rerank_k (k <= rerank_k <= 1,024) best by int8 score are re-scored by
+ * rfx_ivf_search_rerank's rule against rows_d and the k best returned (score desc, row asc). */
+int rfx_ivf_deep_rerank_workspace_bytes(rfx_ivf_t h, int64_t nq, int k, int nprobe, int rerank_k,
+                                        size_t* out_bytes);
+int rfx_ivf_search_deep_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe,
+                               int rerank_k, const void* rows_d, int rows_dtype, const uint32_t* row_mask_d,
+                               int64_t mask_words, float* out_scores_d, int64_t* out_rows_d, void* ws_d,
+                               size_t ws_bytes, void* stream);
+/* Host only: the slab stride (keys per question) of the deep search for list offsets off_h [nlist + 1]. */
+int rfx_ivf_deep_qcap(const int64_t* off_h, int nlist, int nprobe, int64_t* out);
 /* int8 quantisation of rows (the IVF code format): codes [n][dim], inv [n] = amax / 127 */
 int rfx_quantize(const void* rows_d, int64_t n, int dim, int dtype, int8_t* codes_d, float* inv_d,
                  void* stream);

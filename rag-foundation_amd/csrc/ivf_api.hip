@@ -17,6 +17,7 @@
 #include <mutex>
 #include <vector>
 
+#include "k_ivf_deep.h"
 #include "rfx_kernels.h"
 
 namespace {
@@ -45,6 +46,9 @@ struct Ivf {
   float* linv = nullptr;
   int* lids = nullptr;
   int64_t* off = nullptr;  // [nlist + 1]
+  // deep search (k_ivf_deep.h): the rows of the j longest lists at the last build, and the rows it saw
+  int64_t top[rfx::ivf::kDeepMaxProbe + 1] = {0};
+  int64_t built_rows = 0;
   ~Ivf() {
     for (void* p : {(void*)qc, (void*)fc, (void*)codes, (void*)inv, (void*)labels, (void*)lcodes, (void*)linv,
                     (void*)lids, (void*)off})
@@ -93,6 +97,10 @@ int assign_all(Ivf& iv, int64_t r0, int64_t n, hipStream_t st) {
     return api_fail(RFX_EUNSUPPORTED, "assignment launch rejected");
   IVF_HIP(hipGetLastError());
   iv.dirty = true;
+  if (r0 == 0) {  // every row moved: the last build's list lengths bound nothing
+    std::fill(std::begin(iv.top), std::end(iv.top), (int64_t)0);
+    iv.built_rows = 0;
+  }
   return RFX_OK;
 }
 
@@ -133,6 +141,11 @@ int build(Ivf& iv, hipStream_t st) {
   (void)hipFree(tmp);
   if (rc) return api_fail(RFX_EDEVICE, "posting-list build failed (%d)", rc);
   if (e != hipSuccess) return api_fail(RFX_EDEVICE, "posting-list build: %s", hipGetErrorString(e));
+  // the list lengths, once per build (the stream is idle): the deep search sizes its slab by the longest lists
+  std::vector<int64_t> off_h((size_t)iv.nlist + 1);
+  IVF_HIP(hipMemcpy(off_h.data(), iv.off, off_h.size() * 8, hipMemcpyDeviceToHost));
+  rfx::ivf::deep_top_lists(off_h.data(), iv.nlist, iv.top);
+  iv.built_rows = n;
   iv.dirty = false;
   return RFX_OK;
 }
@@ -618,6 +631,184 @@ int rfx_rerank_candidates(const void* queries_d, int64_t nq, int dtype, const vo
                               st, row_lo, n_rows))
     return api_fail(RFX_EUNSUPPORTED, "re-rank launch rejected");
   IVF_HIP(hipGetLastError());
+  return RFX_OK;
+}
+
+}  // extern "C"
+
+// ---- deep search through the lists: k in 65..1,024 (include/rfx.h; kernels k_ivf_deep.h) ---------
+namespace {
+
+struct IvfDeepLayout {
+  int splits;
+  int64_t qcap;
+  size_t qq, qinv, S, Sid, ps, pid, poff, pairs, pbase, nkeys, slab, total;
+};
+
+bool deep_k_ok(int k) { return k >= rfx::kDeepMinK && k <= rfx::kDeepMaxK; }
+
+// The arrays of steps 1-4 as ivf_layout's, then pair_base, n_keys and the slab (nq * qcap keys).  On a dirty
+// index qcap is the bound of deep_qcap (the last build's longest lists plus the rows added since), never less than
+// what the search, which builds first, then needs.
+int ivf_deep_layout(const Ivf& iv, int64_t nq, int nprobe, IvfDeepLayout& L) {
+  if (nprobe < 1 || nprobe > rfx::ivf::kDeepMaxProbe || nprobe > iv.nlist)
+    return api_fail(RFX_EINVAL, "nprobe=%d out of range [1, min(64, nlist=%d)]", nprobe, iv.nlist);
+  if (nq < 0 || nq * nprobe > (int64_t)INT32_MAX / 4) return api_fail(RFX_EINVAL, "nq=%lld out of range", (long long)nq);
+  L.splits = ivf_splits(iv);
+  L.qcap = rfx::ivf::deep_qcap(iv.top, nprobe, iv.rows, iv.built_rows);
+  size_t o = 0;
+  L.qq = o, o += al256((size_t)nq * iv.dim);
+  L.qinv = o, o += al256((size_t)nq * 4);
+  L.S = o, o += al256((size_t)nq * iv.nlist * 4);
+  L.Sid = o, o += al256((size_t)nq * iv.nlist * 4);
+  L.ps = o, o += al256((size_t)nq * nprobe * 4);
+  L.pid = o, o += al256((size_t)nq * nprobe * 8);
+  L.poff = o, o += al256((size_t)(iv.nlist + 1) * 4);
+  L.pairs = o, o += al256((size_t)nq * nprobe * 4);
+  L.pbase = o, o += al256((size_t)nq * nprobe * 4);
+  L.nkeys = o, o += al256((size_t)nq * 4);
+  L.slab = o, o += al256((size_t)nq * (size_t)L.qcap * 8);
+  L.total = o;
+  return RFX_OK;
+}
+
+int ivf_search_deep(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe,
+                    const uint32_t* row_mask_d, int64_t mask_words, float* out_scores_d, int64_t* out_rows_d, void* ws_d,
+                    size_t ws_bytes, void* stream) {
+  if (!deep_k_ok(k)) return api_fail(RFX_EINVAL, "k=%d out of range [65, 1024]", k);
+  auto iv = get(h);
+  if (!iv) return api_fail(RFX_EINVAL, "unknown IVF handle");
+  if (!valid_dtype(dtype)) return api_fail(RFX_EINVAL, "bad query dtype");
+  std::lock_guard<std::mutex> lk(iv->mu);
+  IvfDeepLayout L;
+  int rc = ivf_deep_layout(*iv, nq, nprobe, L);
+  if (rc) return rc;
+  if (nq == 0) return RFX_OK;
+  if (!queries_d || !out_scores_d || !out_rows_d) return api_fail(RFX_EINVAL, "null queries / outputs");
+  if (!iv->trained) return api_fail(RFX_EINVAL, "IVF index not trained");
+  // every row id the scan looks up is below iv->rows, so this is the bound of the mask reads
+  if (row_mask_d && mask_words < (iv->rows + 31) / 32)
+    return api_fail(RFX_EINVAL, "row mask has %lld words, the index needs %lld", (long long)mask_words,
+                    (long long)((iv->rows + 31) / 32));
+  IVF_HIP(hipSetDevice(iv->device));
+  hipStream_t st = (hipStream_t)stream;
+  if ((rc = build(*iv, st))) return rc;
+  if ((rc = ivf_deep_layout(*iv, nq, nprobe, L))) return rc;  // (the lists are current: the exact stride)
+  if (!ws_d || ws_bytes < L.total || ((uintptr_t)ws_d & 15))
+    return api_fail(RFX_EINVAL, "workspace too small (%zu < %zu)", ws_d ? ws_bytes : (size_t)0, L.total);
+  uint8_t* ws = (uint8_t*)ws_d;
+  int8_t* qq = (int8_t*)(ws + L.qq);
+  float* qinv = (float*)(ws + L.qinv);
+  float* S = (float*)(ws + L.S);
+  int* Sid = (int*)(ws + L.Sid);
+  float* ps = (float*)(ws + L.ps);
+  int64_t* pid = (int64_t*)(ws + L.pid);
+  int* poff = (int*)(ws + L.poff);
+  int* pairs = (int*)(ws + L.pairs);
+  int* pbase = (int*)(ws + L.pbase);
+  int* nkeys = (int*)(ws + L.nkeys);
+  uint64_t* slab = (uint64_t*)(ws + L.slab);
+  rfx::ivf::launch_quantize(queries_d, nq, iv->dim, dtype, qq, qinv, st);
+  if (rfx::ivf::launch_coarse_scores(qq, nq, iv->qc, iv->nlist, iv->dim, iv->fc, S, Sid, st))
+    return api_fail(RFX_EUNSUPPORTED, "coarse scoring launch rejected");
+  if (rfx::ivf::launch_probe_select(S, nq, iv->nlist, nprobe, ps, pid, st) != 0 &&
+      rfx::launch_topk_merge(S, Sid, 0, nq, iv->nlist, nprobe, 0, ps, pid, st))
+    return api_fail(RFX_EUNSUPPORTED, "probe selection rejected (nprobe=%d)", nprobe);
+  if (rfx::ivf::launch_group_pairs(pid, (int)(nq * nprobe), iv->nlist, poff, pairs, st))
+    return api_fail(RFX_EUNSUPPORTED, "pair grouping rejected");
+  rfx::ivf::launch_pair_base(pid, iv->off, nq, nprobe, pbase, nkeys, st);
+  if (rfx::ivf::launch_list_score(iv->dim, iv->nlist, L.splits, iv->lcodes, iv->linv, iv->lids, iv->off, poff, pairs, nprobe,
+                                  qq, qinv, pbase, L.qcap, slab, row_mask_d, st))
+    return api_fail(RFX_EUNSUPPORTED, "list score launch rejected (dim=%d)", iv->dim);
+  if (rfx::ivf::launch_deep_select(slab, L.qcap, nkeys, nq, k, out_scores_d, out_rows_d, st))
+    return api_fail(RFX_EUNSUPPORTED, "deep selection rejected (k=%d)", k);
+  IVF_HIP(hipGetLastError());
+  return RFX_OK;
+}
+
+size_t deep_rerank_head(int64_t nq, int rerank_k) { return 3 * al256((size_t)nq * rerank_k * 8); }
+
+}  // namespace
+
+extern "C" {
+
+// On an index with rows added since the last build the answer is the bound of ivf_deep_layout, not the size after
+// a build: this call takes no stream and launches nothing.  rfx_ivf_build first gives the exact size.
+int rfx_ivf_search_deep_workspace_bytes(rfx_ivf_t h, int64_t nq, int k, int nprobe, size_t* out_bytes) {
+  if (!deep_k_ok(k)) return api_fail(RFX_EINVAL, "k=%d out of range [65, 1024]", k);
+  auto iv = get(h);
+  if (!iv) return api_fail(RFX_EINVAL, "unknown IVF handle");
+  if (!out_bytes) return api_fail(RFX_EINVAL, "null out");
+  std::lock_guard<std::mutex> lk(iv->mu);
+  IvfDeepLayout L;
+  int rc = ivf_deep_layout(*iv, nq, nprobe, L);
+  if (rc) return rc;
+  *out_bytes = L.total;
+  return RFX_OK;
+}
+
+int rfx_ivf_search_deep(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe,
+                        const uint32_t* row_mask_d, int64_t mask_words, float* out_scores_d, int64_t* out_rows_d,
+                        void* ws_d, size_t ws_bytes, void* stream) {
+  return ivf_search_deep(h, queries_d, nq, dtype, k, nprobe, row_mask_d, mask_words, out_scores_d, out_rows_d, ws_d,
+                         ws_bytes, stream);
+}
+
+int rfx_ivf_deep_rerank_workspace_bytes(rfx_ivf_t h, int64_t nq, int k, int nprobe, int rerank_k, size_t* out_bytes) {
+  if (!deep_k_ok(k)) return api_fail(RFX_EINVAL, "k=%d out of range [65, 1024]", k);
+  if (rerank_k < k || rerank_k > rfx::kDeepMaxK)
+    return api_fail(RFX_EINVAL, "rerank_k=%d must be in [k=%d, 1024]", rerank_k, k);
+  size_t ivf = 0;
+  int rc = rfx_ivf_search_deep_workspace_bytes(h, nq, rerank_k, nprobe, &ivf);
+  if (rc) return rc;
+  if (!out_bytes) return api_fail(RFX_EINVAL, "null out");
+  *out_bytes = deep_rerank_head(nq, rerank_k) + ivf;
+  return RFX_OK;
+}
+
+// The rerank_k best by int8 score (rfx_ivf_search_deep under the mask), re-scored by rfx_ivf_search_rerank's rule
+// (launch_rerank: the f32 FMA dot of the original rows), then ordered (score desc, row asc) by one LDS sort per
+// question.  Workspace: the three candidate arrays first, the int8 stage's workspace behind them.
+int rfx_ivf_search_deep_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, int k, int nprobe, int rerank_k,
+                               const void* rows_d, int rows_dtype, const uint32_t* row_mask_d, int64_t mask_words,
+                               float* out_scores_d, int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream) {
+  if (!deep_k_ok(k)) return api_fail(RFX_EINVAL, "k=%d out of range [65, 1024]", k);
+  if (rerank_k < k || rerank_k > rfx::kDeepMaxK)
+    return api_fail(RFX_EINVAL, "rerank_k=%d must be in [k=%d, 1024]", rerank_k, k);
+  auto iv = get(h);
+  if (!iv) return api_fail(RFX_EINVAL, "unknown IVF handle");
+  if (!valid_dtype(rows_dtype) || !valid_dtype(dtype)) return api_fail(RFX_EINVAL, "bad dtype");
+  if (nq < 0) return api_fail(RFX_EINVAL, "nq=%lld out of range", (long long)nq);
+  if (nq == 0) return RFX_OK;
+  if (!rows_d || !queries_d || !out_scores_d || !out_rows_d) return api_fail(RFX_EINVAL, "null pointers");
+  const size_t head = deep_rerank_head(nq, rerank_k), part = head / 3;
+  if (!ws_d || ws_bytes < head) return api_fail(RFX_EINVAL, "workspace too small (%zu < %zu)", ws_d ? ws_bytes : (size_t)0, head);
+  uint8_t* ws = (uint8_t*)ws_d;
+  float* cs = (float*)ws;
+  int64_t* cr = (int64_t*)(ws + part);
+  float* rs = (float*)(ws + 2 * part);
+  int64_t* rr = cr;  // the re-rank kernel rewrites rows in place (padding -> empty sentinel)
+  int rc = ivf_search_deep(h, queries_d, nq, dtype, rerank_k, nprobe, row_mask_d, mask_words, cs, cr, ws + head,
+                           ws_bytes - head, stream);
+  if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  IVF_HIP(hipSetDevice(iv->device));
+  if (rfx::ivf::launch_rerank(queries_d, dtype, rows_d, rows_dtype, iv->dim, cr, nq, rerank_k, rs, rr, st))
+    return api_fail(RFX_EUNSUPPORTED, "re-rank launch rejected");
+  if (rfx::ivf::launch_deep_order(rs, rr, nq, rerank_k, k, out_scores_d, out_rows_d, st))
+    return api_fail(RFX_EUNSUPPORTED, "deep order rejected (k=%d)", k);
+  IVF_HIP(hipGetLastError());
+  return RFX_OK;
+}
+
+// Host only: the slab stride of the deep search for the list offsets off_h [nlist + 1] (all rows built).
+int rfx_ivf_deep_qcap(const int64_t* off_h, int nlist, int nprobe, int64_t* out) {
+  if (!off_h || !out || nlist < 1 || nprobe < 1 || nprobe > rfx::ivf::kDeepMaxProbe || nprobe > nlist)
+    return api_fail(RFX_EINVAL, "bad arguments (nlist=%d nprobe=%d)", nlist, nprobe);
+  int64_t top[rfx::ivf::kDeepMaxProbe + 1];
+  rfx::ivf::deep_top_lists(off_h, nlist, top);
+  const int64_t rows = off_h[nlist] - off_h[0];
+  *out = rfx::ivf::deep_qcap(top, nprobe, rows, rows);
   return RFX_OK;
 }
 

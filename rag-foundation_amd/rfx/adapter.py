@@ -162,7 +162,7 @@ class LocalGpuRag:
                  hybrid: Optional[Any] = None, distinct: Optional[Any] = None, top_k: Optional[int] = None):
         """Top-k hits.  k: the request's top_k (the reference route drops it,
         chat.py:66), default self.top_k; 1..64.  top_k (keyword; in place of k): 1..1024 — above 64 the hits are
-        GpuRetriever.candidates' (the deep search: flat bf16 / f16 stores, no diversity, hybrid or distinct;
+        GpuRetriever.candidates' (the deep search: flat bf16 / f16 stores, IVF ones under RFX_IVF_DEEP=1; no diversity, hybrid or distinct;
         what a re-ranking stage reads), up to 64 the same as k.  diversity: a lambda in [0, 1] or {"lambda": ..,
         "fetch_k": ..} picks the k hits by MMR from the fetch_k best (GpuRetriever.search); None = the
         default of RFX_MMR_LAMBDA (unset: off).  hybrid: an alpha in [0, 1] or {"alpha", "fetch_k", "rrf_c",

@@ -266,6 +266,59 @@ class IvfIndex:
         return self._rerank(q, dt, k, nprobe, ctypes.c_void_p(index.data_ptr()), _lib.DTYPE_CODES[index.dtype],
                             rerank_k, stream, row_mask, self._multi(q.shape[0], nprobe, row_masks, mask_of, nprobes))
 
+    # ---- deep search: k in 65..1,024 through the lists ---------------------------------
+    def deep_workspace_bytes(self, nq: int, k: int, nprobe: int, rerank_k: int = None) -> int:
+        """Workspace of search_deep (rerank_k None) or of the re-ranked form.  With rows added since the last
+        build() it is a bound, not the exact size (rfx_ivf_search_deep_workspace_bytes)."""
+        b = ctypes.c_size_t()
+        if rerank_k is None:
+            check(lib.rfx_ivf_search_deep_workspace_bytes(self.handle, int(nq), int(k), int(nprobe), ctypes.byref(b)))
+        else:
+            check(lib.rfx_ivf_deep_rerank_workspace_bytes(self.handle, int(nq), int(k), int(nprobe), int(rerank_k),
+                                                          ctypes.byref(b)))
+        return b.value
+
+    def search_deep(self, queries: torch.Tensor, k: int, nprobe: int, row_mask: torch.Tensor = None,
+                    workspace: torch.Tensor = None, stream=None):
+        """Top-k rows per query over the nprobe nearest lists for k in 65..1024 (rfx_ivf_search_deep): (scores
+        f32 [nq][k], rows i64 [nq][k]) on the device, padded (-inf, -1); the int8 scores and the order of
+        search().  row_mask: as search."""
+        q, dt = self._rows(queries)
+        nq = q.shape[0]
+        m, mw = self._mask(row_mask)
+        out_s = torch.empty((nq, k), dtype=torch.float32, device=self._dev())
+        out_r = torch.empty((nq, k), dtype=torch.int64, device=self._dev())
+        self.build(stream)  # the lists current: the workspace is then the exact size, not the bound
+        need = self.deep_workspace_bytes(nq, k, nprobe)
+        ws = workspace if workspace is not None and workspace.numel() >= need else \
+            torch.empty(max(need, 1), dtype=torch.uint8, device=self._dev())
+        with torch.cuda.device(self.device):
+            check(lib.rfx_ivf_search_deep(self.handle, ptr(q), nq, dt, int(k), int(nprobe), m, mw, ptr(out_s),
+                                          ptr(out_r), ptr(ws), ws.numel(), stream_ptr(stream)))
+        return out_s, out_r
+
+    def search_deep_index(self, queries: torch.Tensor, k: int, nprobe: int, index, rerank_k: int = None,
+                          row_mask: torch.Tensor = None, stream=None):
+        """search_deep keeping rerank_k candidates (default min(1024, 2k)), re-scored in f32 against the rows of
+        a DeviceIndex holding the same rows in the same order, as search_index (rfx_ivf_search_deep_rerank)."""
+        q, dt = self._rows(queries)
+        if index.dim != self.dim or index.device != self.device:
+            raise ValueError("index dim / device differ from the IVF index")
+        if index.rows < self.rows:
+            raise ValueError(f"index holds {index.rows} rows, the IVF lists {self.rows}")
+        rk = min(1024, 2 * int(k)) if rerank_k is None else int(rerank_k)
+        nq = q.shape[0]
+        m, mw = self._mask(row_mask)
+        out_s = torch.empty((nq, k), dtype=torch.float32, device=self._dev())
+        out_r = torch.empty((nq, k), dtype=torch.int64, device=self._dev())
+        self.build(stream)
+        ws = torch.empty(max(self.deep_workspace_bytes(nq, k, nprobe, rk), 1), dtype=torch.uint8, device=self._dev())
+        with torch.cuda.device(self.device):
+            check(lib.rfx_ivf_search_deep_rerank(self.handle, ptr(q), nq, dt, int(k), int(nprobe), rk,
+                                                 ctypes.c_void_p(index.data_ptr()), _lib.DTYPE_CODES[index.dtype], m, mw,
+                                                 ptr(out_s), ptr(out_r), ptr(ws), ws.numel(), stream_ptr(stream)))
+        return out_s, out_r
+
     def train_from(self, index, row_ids, iters: int = 10) -> None:
         """k-means over the rows `row_ids` (sorted int64 numpy array) of a DeviceIndex."""
         import numpy as np
@@ -314,6 +367,15 @@ def rerank_candidates(queries: torch.Tensor, rows_ptr: int, rows_dtype: str, row
                                         _lib.DTYPE_CODES[rows_dtype], int(row_lo), int(n_rows), q.shape[1], ptr(c),
                                         nc, ptr(out_s), ptr(out_r), stream_ptr(stream)))
     return out_s, out_r
+
+
+def deep_qcap(offsets, nprobe: int) -> int:
+    """Host only (rfx_ivf_deep_qcap): keys per question of the deep search's slab for the list offsets
+    [nlist + 1] — the rows of the nprobe longest lists, rounded up to an even count, at least 2."""
+    off = (ctypes.c_int64 * len(offsets))(*[int(v) for v in offsets])
+    out = ctypes.c_int64()
+    check(lib.rfx_ivf_deep_qcap(off, len(offsets) - 1, int(nprobe), ctypes.byref(out)))
+    return out.value
 
 
 def quantize(rows: torch.Tensor, stream=None):

@@ -13,7 +13,7 @@ from . import filters
 from .batcher import GroupBatcher
 from .distinct import DISTINCT_ERROR, parse_distinct
 from .embedder import DEFAULT_MAX_TOKENS, DEFAULT_OVERLAP, Embedder, featurize_texts
-from .store import ivf_filtered_mode, ivf_multi_mode, registry as default_registry
+from .store import ivf_deep_mode, ivf_filtered_mode, ivf_multi_mode, registry as default_registry
 from . import union as runion
 
 
@@ -179,9 +179,11 @@ DEEP_ERROR = "candidates beyond 64 need flat bf16 / f16 single-device stores"
 
 
 def _deep_ok(st) -> bool:
-    """A flat bf16 / f16 store on one device: its index runs the deep search (DeviceIndex.search_deep)."""
-    return hasattr(st.index, "search_deep") and getattr(st, "spec", {}).get("kind", "flat") == "flat" and \
-        st.dtype in ("bf16", "f16")
+    """A flat bf16 / f16 store on one device: its index runs the deep search (DeviceIndex.search_deep).  With
+    RFX_IVF_DEEP=1 an IVF store of such rows too (LocalStore.search_deep: through its lists)."""
+    kind = getattr(st, "spec", {}).get("kind", "flat")
+    return hasattr(st.index, "search_deep") and st.dtype in ("bf16", "f16") and \
+        (kind == "flat" or (kind == "ivf" and ivf_deep_mode() and hasattr(st, "search_deep")))
 
 
 class _StoreAnswer(tuple):
@@ -840,9 +842,10 @@ class GpuRetriever:
     def candidates(self, store_names, question, k, metadata_filter=None):
         """The k best hits for 1 <= k <= 1024, rank order (score desc, store order, row asc): the candidate
         set of a stage behind the retriever (re-ranking, rank fusion, recall@100).  Up to 64 it is search();
-        above, each named store answers with the deep search (DeviceIndex.search_deep, exact) under its own
-        lock and row numbering, and the answers are merged.  ValueError (DEEP_ERROR) on a sharded, IVF or f32
-        store."""
+        above, each named store answers with the deep search (LocalStore.search_deep: DeviceIndex.search_deep,
+        exact, or the lists of an IVF store under RFX_IVF_DEEP=1) under its own lock and row numbering, and the
+        answers are merged.  ValueError (DEEP_ERROR) on a sharded or f32 store, and on an IVF store without
+        RFX_IVF_DEEP=1."""
         k = int(k)
         if not 1 <= k <= 1024:
             raise ValueError(f"k={k} out of range [1, 1024]")
@@ -867,7 +870,11 @@ class GpuRetriever:
                     return None
                 with torch.cuda.device(st.device), st.lock:  # no append moves the rows under the scan
                     q = self.embedder(st.dim).embed_texts([question], st.dtype)
-                    s, r = st.index.search_deep(q, k, row_mask=mask)
+                    if hasattr(st, "search_deep"):  # LocalStore: the lists of an IVF store, else the flat scan
+                        sel = sum(n for _, n in st.mask_ranges(filt)) if mask is not None else None
+                        s, r = st.search_deep(q, k, row_mask=mask, selected=sel)
+                    else:
+                        s, r = st.index.search_deep(q, k, row_mask=mask)
                     return s[0].cpu().tolist(), r[0].cpu().tolist()
 
             res, gen = _numbered(st, run)

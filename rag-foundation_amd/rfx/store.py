@@ -153,6 +153,13 @@ def ivf_multi_mode() -> bool:
     return os.environ.get("RFX_IVF_MULTI", "1").strip() != "0"
 
 
+def ivf_deep_mode() -> bool:
+    """RFX_IVF_DEEP: 0 (default) = candidates beyond 64 of an IVF store are refused (retriever.DEEP_ERROR); 1 = a
+    single-device IVF store of bf16 / f16 rows answers them through its lists (LocalStore.search_deep, DESIGN
+    §4.19).  Read at every question."""
+    return os.environ.get("RFX_IVF_DEEP", "0").strip() == "1"
+
+
 def ivf_filter_nprobe(nprobe, nlist, selected, live, mode):
     """Probe count of a filtered IVF search, or None for the exact path.  A filter that keeps
     `selected` of the `live` rows leaves a fixed nprobe scanning selected / live of the eligible rows an
@@ -913,6 +920,24 @@ class LocalStore:
                                                  rerank_k=min(64, max(16, 2 * int(k))))
                     return s.cpu(), r.cpu()
         return self.index.search(queries, k, row_mask=row_mask)
+
+    def search_deep(self, queries, k, row_mask=None, selected=None):
+        """(scores, rows) on the device of the top-k rows per query for k in 65..1024.  An IVF store whose lists
+        are caught up answers from them (IvfIndex.search_deep_index: the store's probe count, exact re-rank of
+        min(1024, 2k) candidates).  Under a row mask the probe count is ivf_filter_nprobe's over `selected`, the
+        rows the mask selects, by the RFX_IVF_FILTERED rule of search_filtered; mode 0, a probe count past the
+        cap or no `selected` keep the masked flat deep search.  A flat store, or lists that are not trained or
+        behind: DeviceIndex.search_deep, exact."""
+        with self.lock:  # the re-rank reads the DeviceIndex rows in place: no append meanwhile
+            if self.ivf is not None and self.ivf_ready():
+                nprobe = int(self.spec["nprobe"])
+                if row_mask is not None:
+                    live = len(self.rows) - self.dead_rows()
+                    nprobe = None if selected is None else \
+                        ivf_filter_nprobe(nprobe, self.spec["nlist"], selected, live, ivf_filtered_mode())
+                if nprobe is not None:
+                    return self.ivf.search_deep_index(queries, k, nprobe, self.index, row_mask=row_mask)
+            return self.index.search_deep(queries, k, row_mask=row_mask)
 
     def filtered_nprobe(self, metadata_filter):
         """The probe count at which a question under this filter takes the posting lists, or None when it
