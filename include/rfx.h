@@ -278,6 +278,22 @@ int rfx_search_deep(rfx_index_t h, const void* queries_d, int64_t nq, int k, con
  * 128 / 256 / 512 / 1024; a workgroup's candidate buffers take questions * 2 * KB * 8 bytes of LDS.  Same
  * errors as rfx_search_deep. */
 int rfx_deep_plan(int64_t rows, int dim, int dtype, int64_t nq, int k, int* out /* [4] */);
+/* Deep search, sampled threshold: rfx_search_deep's answer — same arguments, score rule, order,
+ * padding, argument checks and error codes — by another route: the k-th best score of a strided sample of the
+ * rows is fixed as the threshold before the scan, one staged pass over the rows then serves 64 or 128 questions
+ * and writes the rows at or above the threshold as keys, and a selection picks the k best.  A question whose
+ * keys overflow its slab is answered by rfx_search_deep's kernels inside the same call (no host wait), so the
+ * answer is exact in every case.  ws_d: 256-byte aligned, rfx_search_deep_sampled_workspace_bytes; after the call
+ * its first int32 holds the number of questions that took that fallback. */
+int rfx_search_deep_sampled_workspace_bytes(rfx_index_t h, int64_t nq, int k, size_t* out_bytes);
+int rfx_search_deep_sampled(rfx_index_t h, const void* queries_d, int64_t nq, int k,
+                            const uint32_t* row_mask_d /* may be NULL */, float* out_scores_d, int64_t* out_rows_d,
+                            void* ws_d, size_t ws_bytes, void* stream);
+/* Host only: the plan rfx_search_deep_sampled would use.  out[6] = {dense, S, stride, cap, questions per
+ * workgroup, row ranges}: dense = 1 for a store of at most 8 * KB rows (one pass writes every row's key, no
+ * sample: S = 0); else the sample is the S rows i * stride and a question's slab takes cap keys in the main pass.
+ * Same errors as rfx_search_deep. */
+int rfx_deep_sampled_plan(int64_t rows, int dim, int dtype, int64_t nq, int k, int* out /* [6] */);
 /* Merge per-query candidate lists into the final top-k.  rows are int32 (rows_are_i64 = 0) or
  * int64 (1); row_offset is added to every returned row (shard base for multi-GPU). */
 int rfx_topk_merge(const float* cand_scores_d, const void* cand_rows_d, int rows_are_i64,

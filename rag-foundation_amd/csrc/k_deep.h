@@ -34,7 +34,10 @@ namespace rfx {
 
 // ws: [nq][p.ranges][p.kb] u64 keys (deep_ws_bytes).  mask: optional row bitmap (rfx_search_masked's form).
 // Returns 0, or -1 for arguments no kernel serves (nothing launched).
+// nq_dev (optional, device): the questions to answer are the first min(nq, *nq_dev), a count that only the device
+// knows when the call is enqueued (the fallback of k_deep_sampled.h); the grid is nq's, groups past the count exit.
 int launch_deep_search(const DeepPlan& p, const void* X, int64_t nrows, int D, int dtype, const void* Q, int64_t nq, int k,
-                       const uint32_t* mask, uint64_t* ws, float* out_s, int64_t* out_r, hipStream_t st);
+                       const uint32_t* mask, uint64_t* ws, float* out_s, int64_t* out_r, hipStream_t st,
+                       const int* nq_dev = nullptr);
 
 }  // namespace rfx

@@ -146,9 +146,14 @@ template <int DT, int NDS>
 __global__ __launch_bounds__(kDeepThreads) void deep_scan_kernel(const uint8_t* __restrict__ X, int nrows, int D,
                                                                  const uint8_t* __restrict__ Q, int nq,
                                                                  const uint32_t* __restrict__ mask, DeepPlan P,
-                                                                 uint64_t* __restrict__ ws) {
+                                                                 uint64_t* __restrict__ ws,
+                                                                 const int* __restrict__ nq_dev) {
   extern __shared__ __attribute__((aligned(16))) uint64_t deep_lds[];
   const int QG = P.q_per_wg, KB = P.kb, N = 2 * KB;
+  if (nq_dev) {  // a question count that is known on the device only: groups past it exit at once (uniform)
+    nq = min(nq, *nq_dev);
+    if ((int)blockIdx.y * QG >= nq) return;
+  }
   const DeepBuf B(deep_lds, QG, KB);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 15, g = lane >> 4;
   const int q0 = blockIdx.y * QG;
@@ -207,8 +212,10 @@ __global__ __launch_bounds__(kDeepThreads) void deep_scan_kernel(const uint8_t* 
 __global__ __launch_bounds__(kDeepThreads) void deep_merge_kernel(const uint64_t* __restrict__ ws, int ranges, int KB, int k,
                                                                   const void* __restrict__ X, int nrows, int D, int dtype,
                                                                   const void* __restrict__ Q, float* __restrict__ out_s,
-                                                                  int64_t* __restrict__ out_r) {
+                                                                  int64_t* __restrict__ out_r,
+                                                                  const int* __restrict__ nq_dev) {
   extern __shared__ __attribute__((aligned(16))) uint64_t deep_lds[];
+  if (nq_dev && (int)blockIdx.x >= *nq_dev) return;  // (uniform)
   const DeepBuf B(deep_lds, 1, KB);
   const int tid = threadIdx.x, N = 2 * KB;
   const int64_t q = blockIdx.x;
@@ -257,7 +264,7 @@ __global__ __launch_bounds__(kDeepThreads) void deep_merge_kernel(const uint64_t
 
 template <int DT, int NDS>
 int launch_scan(const DeepPlan& p, const void* X, int nrows, int D, const void* Q, int nq, const uint32_t* mask, uint64_t* ws,
-                hipStream_t st) {
+                const int* nq_dev, hipStream_t st) {
   auto kern = deep_scan_kernel<DT, NDS>;
   const size_t lds = deep_lds_bytes(p.q_per_wg, p.kb);
   if (lds > (size_t)kDeepLdsBudget) return -1;
@@ -265,18 +272,18 @@ int launch_scan(const DeepPlan& p, const void* X, int nrows, int D, const void* 
       hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return -1;
   hipLaunchKernelGGL(kern, dim3((unsigned)p.ranges, (unsigned)p.q_groups), dim3(kDeepThreads), lds, st, (const uint8_t*)X,
-                     nrows, D, (const uint8_t*)Q, nq, mask, p, ws);
+                     nrows, D, (const uint8_t*)Q, nq, mask, p, ws, nq_dev);
   return 0;
 }
 
 template <int DT>
 int launch_scan_dt(const DeepPlan& p, const void* X, int nrows, int D, const void* Q, int nq, const uint32_t* mask,
-                   uint64_t* ws, hipStream_t st) {
+                   uint64_t* ws, const int* nq_dev, hipStream_t st) {
   switch ((D / 64 + 3) / 4) {
-    case 1: return launch_scan<DT, 4>(p, X, nrows, D, Q, nq, mask, ws, st);
-    case 2: return launch_scan<DT, 8>(p, X, nrows, D, Q, nq, mask, ws, st);
-    case 3: return launch_scan<DT, 12>(p, X, nrows, D, Q, nq, mask, ws, st);
-    case 4: return launch_scan<DT, 16>(p, X, nrows, D, Q, nq, mask, ws, st);
+    case 1: return launch_scan<DT, 4>(p, X, nrows, D, Q, nq, mask, ws, nq_dev, st);
+    case 2: return launch_scan<DT, 8>(p, X, nrows, D, Q, nq, mask, ws, nq_dev, st);
+    case 3: return launch_scan<DT, 12>(p, X, nrows, D, Q, nq, mask, ws, nq_dev, st);
+    case 4: return launch_scan<DT, 16>(p, X, nrows, D, Q, nq, mask, ws, nq_dev, st);
   }
   return -1;
 }
@@ -284,19 +291,19 @@ int launch_scan_dt(const DeepPlan& p, const void* X, int nrows, int D, const voi
 }  // namespace
 
 int launch_deep_search(const DeepPlan& p, const void* X, int64_t nrows, int D, int dtype, const void* Q, int64_t nq, int k,
-                       const uint32_t* mask, uint64_t* ws, float* out_s, int64_t* out_r, hipStream_t st) {
+                       const uint32_t* mask, uint64_t* ws, float* out_s, int64_t* out_r, hipStream_t st, const int* nq_dev) {
   if (dtype != RFX_BF16 && dtype != RFX_F16) return -1;
   if (D < 64 || D > kDeepMaxDim || D % 64 != 0) return -1;
   if (nq < 1 || nq > kDeepMaxNq || k < kDeepMinK || k > p.kb || nrows < 0 || nrows > 0x7fffffffll - 1) return -1;
   if (p.ranges < 1 || p.check_rounds < 2 || p.check_rounds % 2 != 0 || 2 * p.kb < p.kb + p.check_rounds * kDeepRound ||
       p.q_per_wg > kDeepQSlots || (int64_t)(p.ranges - 1) * p.rows_per_range > nrows)
     return -1;
-  const int rc = dtype == RFX_BF16 ? launch_scan_dt<RFX_BF16>(p, X, (int)nrows, D, Q, (int)nq, mask, ws, st)
-                                   : launch_scan_dt<RFX_F16>(p, X, (int)nrows, D, Q, (int)nq, mask, ws, st);
+  const int rc = dtype == RFX_BF16 ? launch_scan_dt<RFX_BF16>(p, X, (int)nrows, D, Q, (int)nq, mask, ws, nq_dev, st)
+                                   : launch_scan_dt<RFX_F16>(p, X, (int)nrows, D, Q, (int)nq, mask, ws, nq_dev, st);
   if (rc) return rc;
   const size_t lds = deep_lds_bytes(1, p.kb);
   hipLaunchKernelGGL(deep_merge_kernel, dim3((unsigned)nq), dim3(kDeepThreads), lds, st, ws, p.ranges, p.kb, k, X, (int)nrows,
-                     D, dtype, Q, out_s, out_r);
+                     D, dtype, Q, out_s, out_r, nq_dev);
   return 0;
 }
 

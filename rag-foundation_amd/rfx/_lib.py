@@ -169,6 +169,9 @@ SIGNATURES = {
     "rfx_search_deep_workspace_bytes": ([_u64, _i64, _i, _psz], _i),
     "rfx_search_deep": ([_u64, _p, _i64, _i, _p, _p, _p, _p, _sz, _p], _i),
     "rfx_deep_plan": ([_i64, _i, _i, _i64, _i, _pi], _i),
+    "rfx_search_deep_sampled_workspace_bytes": ([_u64, _i64, _i, _psz], _i),
+    "rfx_search_deep_sampled": ([_u64, _p, _i64, _i, _p, _p, _p, _p, _sz, _p], _i),
+    "rfx_deep_sampled_plan": ([_i64, _i, _i, _i64, _i, _pi], _i),
     "rfx_search_plan": ([_u64, _i64, _i, _pi], _i),
     "rfx_rescore_topk": ([_u64, _p, _i64, _i, _i64, _p, _p, _p, _p], _i),
     "rfx_sharded_search": ([_i, _p, _p, _p, _p, _i64, _i, _p, _p, _p, _p, _p, _p, _u64, _p, _p, _p, _p], _i),

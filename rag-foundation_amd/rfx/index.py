@@ -236,6 +236,35 @@ class DeviceIndex:
                                       ptr(out_r), ptr(ws), ws.numel(), stream_ptr(stream)))
         return out_s, out_r
 
+    def deep_sampled_workspace_bytes(self, nq: int, k: int) -> int:
+        b = ctypes.c_size_t()
+        check(lib.rfx_search_deep_sampled_workspace_bytes(self.handle, int(nq), int(k), ctypes.byref(b)))
+        return b.value
+
+    def search_deep_sampled(self, queries: torch.Tensor, k: int, row_mask: torch.Tensor = None,
+                            workspace: torch.Tensor = None, stream=None, stats: bool = False):
+        """search_deep's answer by the sampled-threshold scan (rfx_search_deep_sampled): one pass
+        over the rows per 64 or 128 questions; a question whose keys overflow is answered by search_deep's kernels
+        inside the call.  stats=True: (scores, rows, questions that fell back) — reading the count waits for the
+        stream."""
+        q = self._check_queries(queries)
+        nq = q.shape[0]
+        dev = q.device
+        need = self.deep_sampled_workspace_bytes(nq, k)
+        out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        ws = workspace if workspace is not None and workspace.numel() >= need else \
+            torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        m, _ = self._check_mask(row_mask, dev)
+        with torch.cuda.device(dev):
+            check(lib.rfx_search_deep_sampled(self.handle, ptr(q), nq, int(k), ptr(m) if m is not None else None,
+                                              ptr(out_s), ptr(out_r), ptr(ws), ws.numel(), stream_ptr(stream)))
+            if stats:
+                if stream is not None:
+                    stream.synchronize()
+                return out_s, out_r, int(ws[:4].view(torch.int32).item()) if nq else 0
+        return out_s, out_r
+
     def search_segmented(self, queries: torch.Tensor, k: int, groups, workspace: torch.Tensor = None, stream=None):
         """One launch for questions under different metadata filters (rfx_search_segmented): `groups` is a
         list of (query_indices, [(first, count), ...]); a query is answered over its group's row ranges only
@@ -595,6 +624,14 @@ def deep_plan(rows: int, dim: int, dtype: str, nq: int, k: int):
     """Host only (rfx_deep_plan): (row ranges, rows per range, KB, questions per workgroup) of a deep search."""
     out = (ctypes.c_int * 4)()
     check(lib.rfx_deep_plan(int(rows), int(dim), _lib.DTYPE_CODES[dtype], int(nq), int(k), out))
+    return tuple(out)
+
+
+def deep_sampled_plan(rows: int, dim: int, dtype: str, nq: int, k: int):
+    """Host only (rfx_deep_sampled_plan): (dense, S, stride, cap, questions per workgroup, row ranges) of a
+    sampled-threshold deep search."""
+    out = (ctypes.c_int * 6)()
+    check(lib.rfx_deep_sampled_plan(int(rows), int(dim), _lib.DTYPE_CODES[dtype], int(nq), int(k), out))
     return tuple(out)
 
 

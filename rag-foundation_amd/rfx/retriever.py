@@ -13,7 +13,7 @@ from . import filters
 from .batcher import GroupBatcher
 from .distinct import DISTINCT_ERROR, parse_distinct
 from .embedder import DEFAULT_MAX_TOKENS, DEFAULT_OVERLAP, Embedder, featurize_texts
-from .store import ivf_deep_mode, ivf_filtered_mode, ivf_multi_mode, registry as default_registry
+from .store import flat_search_deep, ivf_deep_mode, ivf_filtered_mode, ivf_multi_mode, registry as default_registry
 from . import union as runion
 
 
@@ -874,7 +874,7 @@ class GpuRetriever:
                         sel = sum(n for _, n in st.mask_ranges(filt)) if mask is not None else None
                         s, r = st.search_deep(q, k, row_mask=mask, selected=sel)
                     else:
-                        s, r = st.index.search_deep(q, k, row_mask=mask)
+                        s, r = flat_search_deep(st.index, q, k, mask)  # (RFX_DEEP_SAMPLED picks the route)
                     return s[0].cpu().tolist(), r[0].cpu().tolist()
 
             res, gen = _numbered(st, run)

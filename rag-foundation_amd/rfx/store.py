@@ -160,6 +160,20 @@ def ivf_deep_mode() -> bool:
     return os.environ.get("RFX_IVF_DEEP", "0").strip() == "1"
 
 
+def deep_sampled_mode() -> bool:
+    """RFX_DEEP_SAMPLED: 0 (default) = the flat deep search is DeviceIndex.search_deep; 1 = it is
+    DeviceIndex.search_deep_sampled (the sampled-threshold scan, DESIGN §4.20: the same answer).  Read at every
+    question."""
+    return os.environ.get("RFX_DEEP_SAMPLED", "0").strip() == "1"
+
+
+def flat_search_deep(index, queries, k, row_mask=None):
+    """The flat deep search of `index` by the route RFX_DEEP_SAMPLED names."""
+    if deep_sampled_mode():
+        return index.search_deep_sampled(queries, k, row_mask=row_mask)
+    return index.search_deep(queries, k, row_mask=row_mask)
+
+
 def ivf_filter_nprobe(nprobe, nlist, selected, live, mode):
     """Probe count of a filtered IVF search, or None for the exact path.  A filter that keeps
     `selected` of the `live` rows leaves a fixed nprobe scanning selected / live of the eligible rows an
@@ -937,7 +951,7 @@ class LocalStore:
                         ivf_filter_nprobe(nprobe, self.spec["nlist"], selected, live, ivf_filtered_mode())
                 if nprobe is not None:
                     return self.ivf.search_deep_index(queries, k, nprobe, self.index, row_mask=row_mask)
-            return self.index.search_deep(queries, k, row_mask=row_mask)
+            return flat_search_deep(self.index, queries, k, row_mask)
 
     def filtered_nprobe(self, metadata_filter):
         """The probe count at which a question under this filter takes the posting lists, or None when it
