@@ -661,6 +661,25 @@ int rfx_lex_fuse(rfx_lex_t h, const int64_t* dense_rows_d, int n_dense_max, cons
                  int64_t nq, int k, const float* alpha_h, const int32_t* n_dense_h, const int32_t* n_lex_h, int rrf_c,
                  float* out_scores_d, int64_t* out_rows_d, int32_t* out_ranks_d /* may be NULL */, void* stream);
 
+/* ---- lexical index at depth: BM25 top-k and rank fusion for 65..1,024 -----------------------------
+ * What a rank fusion over 100+ entries per list, or the candidate set of a re-ranker, reads.
+ * rfx_lex_search_deep: the arguments, rules, padding and refusals of rfx_lex_search with k in 65..1,024 (any other
+ * k: RFX_EINVAL, nothing enqueued, outputs untouched); a row's score has the bits rfx_lex_search gives it, so the
+ * first 64 entries of an answer are rfx_lex_search's at k = 64.  The workspace must be 16-byte aligned.  Workspace:
+ * the question entries, one weight table per 4 questions (ceil(nq / 4) * 4 * V * 4 bytes), the key slab
+ * (nq * blocks * KB * 8 bytes, KB = k rounded up to 128 / 256 / 512 / 1,024, blocks = 512 / ceil(nq / 4) clamped to
+ * [1, min(256, ceil(rows / 512))]: at most 16 MB) and nq counters.  The environment variable RFX_LEX_DEEP_BLOCKS
+ * (read per call, by both functions) caps `blocks`. */
+int rfx_lex_search_deep_workspace_bytes(rfx_lex_t h, int64_t nq, int k, size_t* out_bytes);
+int rfx_lex_search_deep(rfx_lex_t h, const int32_t* q_indptr_h, const int32_t* q_bucket_h, const int16_t* q_count_h,
+                        int64_t nq, int k, float k1, float b, const uint32_t* mask_d, int64_t mask_words,
+                        float* scores_d, int64_t* rows_d, void* ws, size_t ws_bytes, void* stream);
+/* rfx_lex_fuse's rule and refusals with list lengths 1..1,024 and k in 1..1,024 (k <= n_dense_max + n_lex_max,
+ * nq in 1..1024).  A row repeated inside one list keeps its first rank; every valid entry advances the rank. */
+int rfx_lex_fuse_deep(rfx_lex_t h, const int64_t* dense_rows_d, int n_dense_max, const int64_t* lex_rows_d, int n_lex_max,
+                      int64_t nq, int k, const float* alpha_h, const int32_t* n_dense_h, const int32_t* n_lex_h, int rrf_c,
+                      float* out_scores_d, int64_t* out_rows_d, int32_t* out_ranks_d /* may be NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,23 @@ namespace rfx {
 
 constexpr int kFuseMaxList = 64;
 
+// (device; shared with k_fuse_deep.hip: one definition, the same bits at every depth)
+// f = A / (c + rank_d) + (1 - A) / (c + rank_l): IEEE f64 divisions, no contraction; rank 0 = absent = 0.0
+__device__ __forceinline__ double rrf_score(double A, double c, int rank_d, int rank_l) {
+#pragma clang fp contract(off)
+  double fd = 0.0, fl = 0.0;
+  if (rank_d > 0) {
+    const double den = c + (double)rank_d;
+    fd = A / den;
+  }
+  if (rank_l > 0) {
+    const double oma = 1.0 - A;
+    const double den = c + (double)rank_l;
+    fl = oma / den;
+  }
+  return fd + fl;
+}
+
 // One wave per question.  dense_r / lex_r: [nq][n_dense_max] / [nq][n_lex_max] rows (< 0 = padding), of which
 // the first nd[q] / nl[q] entries are used; alpha [nq] f32.  out_s / out_r [nq][k]; out_ranks (may be null)
 // [nq][k][2] = {rank_d, rank_l}, 0 = absent.  Padding (-inf, -1, 0, 0).

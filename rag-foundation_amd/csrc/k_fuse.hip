@@ -6,22 +6,6 @@
 namespace rfx {
 namespace {
 
-// f = A / (c + rank_d) + (1 - A) / (c + rank_l): IEEE f64 divisions, no contraction; rank 0 = absent = 0.0
-__device__ __forceinline__ double rrf_score(double A, double c, int rank_d, int rank_l) {
-#pragma clang fp contract(off)
-  double fd = 0.0, fl = 0.0;
-  if (rank_d > 0) {
-    const double den = c + (double)rank_d;
-    fd = A / den;
-  }
-  if (rank_l > 0) {
-    const double oma = 1.0 - A;
-    const double den = c + (double)rank_l;
-    fl = oma / den;
-  }
-  return fd + fl;
-}
-
 // Lane i owns dense entry i and lexical entry i.  Candidates: slot i = dense entry i (with its lexical rank when
 // the row is in both lists), slot 64 + i = lexical entry i when its row is NOT in the dense list.  A candidate's
 // output position is the number of candidates that beat it (rows are distinct, so the order is total).

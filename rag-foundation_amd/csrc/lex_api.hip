@@ -1,11 +1,13 @@
 // lex_api.hip — C ABI of the lexical (BM25) index and the rank fusion (include/rfx.h, "lexical index").
 //
 // One handle owns, on one device: the CSR of every row's hashed term features (indptr, packed entries, len) and,
-// on the host, its mirror with the exact statistics over live rows (lex_host.h).  Kernels: k_lex.hip, k_fuse.hip;
+// on the host, its mirror with the exact statistics over live rows (lex_host.h).  Kernels: k_lex.hip, k_fuse.hip,
+// and k_lex_deep.hip, k_fuse_deep.hip for k in 65..1,024;
 // rules: DESIGN §4.14, restated in numpy by tests/lex_ref.py.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <memory>
@@ -13,7 +15,10 @@
 #include <vector>
 
 #include "k_fuse.h"
+#include "k_fuse_deep.h"
+#include "k_ivf_deep.h"
 #include "k_lex.h"
+#include "k_lex_deep.h"
 #include "rfx_kernels.h"
 
 namespace {
@@ -127,6 +132,28 @@ LexWs lex_ws(const Lex& lx, int64_t nq, int k, int64_t q_nnz_cap) {
 // a question holds at most V distinct buckets; the workspace covers min(V, 4096) per question (a chunk's
 // featurisation has far fewer), a longer batch is refused
 int64_t q_nnz_cap(const Lex& lx, int64_t nq) { return nq * std::min(lx.host.V, 4096); }
+
+struct LexDeepWs {  // workspace layout of a deep search
+  rfx::LexDeepPlan p;
+  size_t off_off, ent_off, w_off, slab_off, nk_off, total;
+};
+// RFX_LEX_DEEP_BLOCKS, read per call: caps the scan's blocks per question group (an A/B switch; 0 / unset: no cap)
+int deep_block_cap() {
+  const char* e = std::getenv("RFX_LEX_DEEP_BLOCKS");
+  return e ? std::max(0, std::atoi(e)) : 0;
+}
+LexDeepWs lex_deep_ws(const Lex& lx, int64_t nq, int k, int64_t q_nnz_cap) {
+  LexDeepWs w{};
+  w.p = rfx::lex_deep_plan(lx.host.rows, lx.host.V, nq, k, deep_block_cap());
+  size_t o = 0;
+  w.off_off = o, o += al256((size_t)(nq + 1) * 4);
+  w.ent_off = o, o += al256((size_t)q_nnz_cap * sizeof(rfx::LexQueryEntry));
+  w.w_off = o, o += al256((size_t)w.p.groups * lx.host.V * w.p.nqt * 4);
+  w.slab_off = o, o += al256((size_t)nq * w.p.blocks * w.p.kb * 8);
+  w.nk_off = o, o += al256((size_t)nq * 4);
+  w.total = o;
+  return w;
+}
 
 }  // namespace
 
@@ -346,6 +373,111 @@ int rfx_lex_fuse(rfx_lex_t h, const int64_t* dense_rows_d, int n_dense_max, cons
   // recorded after the kernel: the next user of the staging buffer or of the device tables waits for both
   LEX_HIP(hipEventRecord(lx->stage_ev, st));
   if (rc != 0) return api_fail(RFX_EUNSUPPORTED, "lex fuse launch rejected");
+  LEX_HIP(hipGetLastError());
+  return RFX_OK;
+}
+
+int rfx_lex_search_deep_workspace_bytes(rfx_lex_t h, int64_t nq, int k, size_t* out_bytes) {
+  auto lx = get(h);
+  if (!lx) return api_fail(RFX_EINVAL, "unknown lexical handle");
+  if (!out_bytes) return api_fail(RFX_EINVAL, "null output");
+  const std::string err = rfx::lex_validate_search(nq, k, 1.2f, 0.75f, rfx::kDeepMinK, rfx::kDeepMaxK);
+  if (!err.empty()) return api_fail(RFX_EINVAL, "lex deep search: %s", err.c_str());
+  std::lock_guard<std::mutex> lk(lx->mu);
+  *out_bytes = lex_deep_ws(*lx, nq, k, q_nnz_cap(*lx, nq)).total;
+  return RFX_OK;
+}
+
+int rfx_lex_search_deep(rfx_lex_t h, const int32_t* q_indptr_h, const int32_t* q_bucket_h, const int16_t* q_count_h,
+                        int64_t nq, int k, float k1, float b, const uint32_t* mask_d, int64_t mask_words,
+                        float* scores_d, int64_t* rows_d, void* ws, size_t ws_bytes, void* stream) {
+  auto lx = get(h);
+  if (!lx) return api_fail(RFX_EINVAL, "unknown lexical handle");
+  std::string err = rfx::lex_validate_search(nq, k, k1, b, rfx::kDeepMinK, rfx::kDeepMaxK);
+  if (!err.empty()) return api_fail(RFX_EINVAL, "lex deep search: %s", err.c_str());
+  std::lock_guard<std::mutex> lk(lx->mu);
+  const rfx::LexHost& H = lx->host;
+  err = rfx::lex_validate_csr(H.V, q_indptr_h, q_bucket_h, q_count_h, nq);
+  if (!err.empty()) return api_fail(RFX_EINVAL, "lex deep search: question %s", err.c_str());
+  if (!scores_d || !rows_d) return api_fail(RFX_EINVAL, "lex deep search: null outputs");
+  if (mask_d && mask_words < (H.rows + 31) / 32)
+    return api_fail(RFX_EINVAL, "row mask has %lld words, the index needs %lld", (long long)mask_words,
+                    (long long)((H.rows + 31) / 32));
+  const int64_t cap = q_nnz_cap(*lx, nq);
+  const LexDeepWs W = lex_deep_ws(*lx, nq, k, cap);
+  if (!ws || ws_bytes < W.total) return api_fail(RFX_EINVAL, "workspace too small (%zu < %zu)", ws_bytes, W.total);
+  if ((uintptr_t)ws & 15) return api_fail(RFX_EINVAL, "workspace not 16-byte aligned");
+  std::vector<int32_t> off;
+  std::vector<rfx::LexQueryEntry> ent;
+  rfx::lex_query_weights(H, q_indptr_h, q_bucket_h, q_count_h, nq, off, ent);
+  if ((int64_t)ent.size() > cap)
+    return api_fail(RFX_EINVAL, "lex deep search: %zu question entries, the workspace holds %lld", ent.size(),
+                    (long long)cap);
+  LEX_HIP(hipSetDevice(lx->device));
+  hipStream_t st = (hipStream_t)stream;
+  uint8_t* w8 = (uint8_t*)ws;
+  if (H.rows == 0 || H.live == 0) {  // nothing can rank
+    rfx::launch_lex_deep_none(scores_d, rows_d, nq * k, st);
+    LEX_HIP(hipGetLastError());
+    return RFX_OK;
+  }
+  {
+    // the question tables through the pinned staging buffer: the caller's arrays may die on return
+    const size_t need = W.ent_off + ent.size() * sizeof(rfx::LexQueryEntry);
+    if (const int rc = stage_acquire(*lx, need)) return rc;
+    uint8_t* s8 = (uint8_t*)lx->stage;
+    std::memcpy(s8 + W.off_off, off.data(), off.size() * 4);
+    if (!ent.empty()) std::memcpy(s8 + W.ent_off, ent.data(), ent.size() * sizeof(rfx::LexQueryEntry));
+    LEX_HIP(hipMemcpyAsync(w8, s8, need, hipMemcpyHostToDevice, st));  // one copy: both tables and the gap
+    LEX_HIP(hipEventRecord(lx->stage_ev, st));
+  }
+  rfx::LexPlan wp{};  // the weight tables at 4 questions per group
+  wp.nqt = W.p.nqt, wp.groups = W.p.groups;
+  rfx::launch_lex_weights(wp, H.V, (const int32_t*)(w8 + W.off_off), (const rfx::LexQueryEntry*)(w8 + W.ent_off), nq,
+                          (float*)(w8 + W.w_off), st);
+  uint64_t* slab = (uint64_t*)(w8 + W.slab_off);
+  int* n_keys = (int*)(w8 + W.nk_off);
+  if (rfx::launch_lex_deep_scan(W.p, H.V, lx->indptr, lx->entries, lx->len, H.rows, (const float*)(w8 + W.w_off), nq,
+                                (double)k1, (double)b, H.avgdl(), mask_d, slab, n_keys, st) != 0)
+    return api_fail(RFX_EUNSUPPORTED, "lex deep scan launch rejected");
+  if (rfx::ivf::launch_deep_select(slab, (int64_t)W.p.blocks * W.p.kb, n_keys, nq, k, scores_d, rows_d, st) != 0)
+    return api_fail(RFX_EUNSUPPORTED, "lex deep search: selection k=%d unsupported", k);
+  LEX_HIP(hipGetLastError());
+  return RFX_OK;
+}
+
+int rfx_lex_fuse_deep(rfx_lex_t h, const int64_t* dense_rows_d, int n_dense_max, const int64_t* lex_rows_d, int n_lex_max,
+                      int64_t nq, int k, const float* alpha_h, const int32_t* n_dense_h, const int32_t* n_lex_h, int rrf_c,
+                      float* out_scores_d, int64_t* out_rows_d, int32_t* out_ranks_d, void* stream) {
+  auto lx = get(h);
+  if (!lx) return api_fail(RFX_EINVAL, "unknown lexical handle");
+  const std::string err = rfx::lex_validate_fuse(n_dense_max, n_lex_max, nq, k, alpha_h, n_dense_h, n_lex_h, rrf_c,
+                                                 rfx::kFuseDeepMaxList);
+  if (!err.empty()) return api_fail(RFX_EINVAL, "lex deep fuse: %s", err.c_str());
+  if (!dense_rows_d || !lex_rows_d || !out_scores_d || !out_rows_d)
+    return api_fail(RFX_EINVAL, "lex deep fuse: null lists / outputs");
+  std::lock_guard<std::mutex> lk(lx->mu);
+  LEX_HIP(hipSetDevice(lx->device));
+  hipStream_t st = (hipStream_t)stream;
+  // the per-question tables {alpha, n_dense, n_lex}, staged as rfx_lex_fuse stages them
+  const size_t tab = al256((size_t)nq * 4);
+  if (const int rc = stage_acquire(*lx, 3 * tab)) return rc;
+  uint8_t* s8 = (uint8_t*)lx->stage;
+  for (int64_t q = 0; q < nq; ++q) {
+    ((float*)s8)[q] = alpha_h ? alpha_h[q] : 0.5f;
+    ((int32_t*)(s8 + tab))[q] = n_dense_h ? n_dense_h[q] : n_dense_max;
+    ((int32_t*)(s8 + 2 * tab))[q] = n_lex_h ? n_lex_h[q] : n_lex_max;
+  }
+  if (!lx->fuse_tab && hipMalloc(&lx->fuse_tab, 3 * al256((size_t)rfx::kLexMaxNq * 4)) != hipSuccess)
+    return api_fail(RFX_ENOMEM, "hipMalloc failed (fusion tables)");
+  uint8_t* t_d = (uint8_t*)lx->fuse_tab;
+  LEX_HIP(hipMemcpyAsync(t_d, s8, 3 * tab, hipMemcpyHostToDevice, st));
+  const int rc = rfx::launch_rrf_fuse_deep(dense_rows_d, n_dense_max, lex_rows_d, n_lex_max, nq, k, (const float*)t_d,
+                                           (const int32_t*)(t_d + tab), (const int32_t*)(t_d + 2 * tab), rrf_c,
+                                           out_scores_d, out_rows_d, out_ranks_d, st);
+  // recorded after the kernel: the next user of the staging buffer or of the device tables waits for both
+  LEX_HIP(hipEventRecord(lx->stage_ev, st));
+  if (rc != 0) return api_fail(RFX_EUNSUPPORTED, "lex deep fuse launch rejected");
   LEX_HIP(hipGetLastError());
   return RFX_OK;
 }

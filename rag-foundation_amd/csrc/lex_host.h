@@ -161,9 +161,11 @@ inline void lex_query_weights(const LexHost& L, const IP* q_indptr, const int32_
 }
 
 // "" when the arguments of a search are acceptable (the question CSR is checked with lex_validate_csr)
-inline std::string lex_validate_search(int64_t nq, int k, float k1, float b) {
+// k_lo .. k_hi: 1..64, or the deep search's 65..1,024
+inline std::string lex_validate_search(int64_t nq, int k, float k1, float b, int k_lo = 1, int k_hi = kLexMaxK) {
   if (nq < 1 || nq > kLexMaxNq) return "nq=" + std::to_string(nq) + " out of [1, 1024]";
-  if (k < 1 || k > kLexMaxK) return "k=" + std::to_string(k) + " out of [1, 64]";
+  if (k < k_lo || k > k_hi)
+    return "k=" + std::to_string(k) + " out of [" + std::to_string(k_lo) + ", " + std::to_string(k_hi) + "]";
   if (!(k1 >= 0.0f) || isinf(k1)) return "k1 must be a finite number >= 0";
   if (!(b >= 0.0f && b <= 1.0f)) return "b outside [0, 1]";
   return "";
@@ -171,11 +173,12 @@ inline std::string lex_validate_search(int64_t nq, int k, float k1, float b) {
 
 // "" when the arguments of a fusion are acceptable; alpha / n_dense / n_lex may be null (0.5, the list maxima)
 inline std::string lex_validate_fuse(int n_dense_max, int n_lex_max, int64_t nq, int k, const float* alpha,
-                                     const int32_t* n_dense, const int32_t* n_lex, int rrf_c) {
+                                     const int32_t* n_dense, const int32_t* n_lex, int rrf_c, int most = kLexMaxK) {
+  const std::string range = " out of [1, " + std::to_string(most) + "]";  // most: 64, or the deep fusion's 1,024
   if (nq < 1 || nq > kLexMaxNq) return "nq=" + std::to_string(nq) + " out of [1, 1024]";
-  if (k < 1 || k > kLexMaxK) return "k=" + std::to_string(k) + " out of [1, 64]";
-  if (n_dense_max < 1 || n_dense_max > 64) return "n_dense_max=" + std::to_string(n_dense_max) + " out of [1, 64]";
-  if (n_lex_max < 1 || n_lex_max > 64) return "n_lex_max=" + std::to_string(n_lex_max) + " out of [1, 64]";
+  if (k < 1 || k > most) return "k=" + std::to_string(k) + range;
+  if (n_dense_max < 1 || n_dense_max > most) return "n_dense_max=" + std::to_string(n_dense_max) + range;
+  if (n_lex_max < 1 || n_lex_max > most) return "n_lex_max=" + std::to_string(n_lex_max) + range;
   if (k > n_dense_max + n_lex_max) return "k > n_dense_max + n_lex_max";
   if (rrf_c < 1) return "rrf_c < 1";
   for (int64_t q = 0; q < nq; ++q) {

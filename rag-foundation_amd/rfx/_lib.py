@@ -206,6 +206,10 @@ SIGNATURES = {
     "rfx_lex_search_workspace_bytes": ([_u64, _i64, _i, _psz], _i),
     "rfx_lex_search": ([_u64, _p, _p, _p, _i64, _i, ctypes.c_float, ctypes.c_float, _p, _i64, _p, _p, _p, _sz, _p], _i),
     "rfx_lex_fuse": ([_u64, _p, _i, _p, _i, _i64, _i, _p, _p, _p, _i, _p, _p, _p, _p], _i),
+    "rfx_lex_search_deep_workspace_bytes": ([_u64, _i64, _i, _psz], _i),
+    "rfx_lex_search_deep": ([_u64, _p, _p, _p, _i64, _i, ctypes.c_float, ctypes.c_float, _p, _i64, _p, _p, _p, _sz,
+                             _p], _i),
+    "rfx_lex_fuse_deep": ([_u64, _p, _i, _p, _i, _i64, _i, _p, _p, _p, _i, _p, _p, _p, _p], _i),
 }
 
 for _name, (_args, _res) in SIGNATURES.items():

@@ -162,8 +162,9 @@ class LocalGpuRag:
                  hybrid: Optional[Any] = None, distinct: Optional[Any] = None, top_k: Optional[int] = None):
         """Top-k hits.  k: the request's top_k (the reference route drops it,
         chat.py:66), default self.top_k; 1..64.  top_k (keyword; in place of k): 1..1024 — above 64 the hits are
-        GpuRetriever.candidates' (the deep search: flat bf16 / f16 stores, IVF ones under RFX_IVF_DEEP=1; no diversity, hybrid or distinct;
-        what a re-ranking stage reads), up to 64 the same as k.  diversity: a lambda in [0, 1] or {"lambda": ..,
+        GpuRetriever.candidates' (the deep search: flat bf16 / f16 stores, IVF ones under RFX_IVF_DEEP=1; hybrid as
+        below, fused at depth on flat stores; no diversity or distinct; what a re-ranking stage reads), up to 64
+        the same as k.  diversity: a lambda in [0, 1] or {"lambda": ..,
         "fetch_k": ..} picks the k hits by MMR from the fetch_k best (GpuRetriever.search); None = the
         default of RFX_MMR_LAMBDA (unset: off).  hybrid: an alpha in [0, 1] or {"alpha", "fetch_k", "rrf_c",
         "k1", "b"} fuses the dense answer with the BM25 answer over the chunk texts (GpuRetriever.search;
@@ -174,7 +175,10 @@ class LocalGpuRag:
         filt = metadata_filter if self.apply_filters else None
         if top_k is not None:
             if int(top_k) > 64:
-                return self.retriever.candidates(list(store_names or []), question, int(top_k), metadata_filter=filt)
+                hyb = self.hybrid if hybrid is None else hybrid
+                kw = {} if hyb is None else {"hybrid": hyb}
+                return self.retriever.candidates(list(store_names or []), question, int(top_k), metadata_filter=filt,
+                                                 **kw)
             k = int(top_k)
         div = self.diversity if diversity is None else diversity
         hyb = self.hybrid if hybrid is None else hybrid

@@ -99,6 +99,22 @@ class LexIndex:
         """BM25 top-k per question: (scores f32 [nq][k], rows int64 [nq][k]) on the device, padded (-inf, -1).
         Questions: a host CSR (indptr, bucket, count) or a list of strings.  row_mask as DeviceIndex.search.
         out: optional (scores, rows) tensors to write into; workspace: overrides the workspace (tests)."""
+        return self._search(lib.rfx_lex_search, self.workspace_bytes, (1, 64), csr_or_texts, k, k1, b, row_mask, stream,
+                            out, workspace)
+
+    def deep_workspace_bytes(self, nq: int, k: int) -> int:
+        b = ctypes.c_size_t()
+        check(lib.rfx_lex_search_deep_workspace_bytes(self.handle, int(nq), int(k), ctypes.byref(b)))
+        return b.value
+
+    def search_deep(self, csr_or_texts, k: int, k1: float = DEFAULT_K1, b: float = DEFAULT_B, row_mask=None,
+                    stream=None, out=None, workspace=None):
+        """search() for k in 65..1024 (rfx_lex_search_deep): the same scores bit for bit, so its
+        first 64 entries are search(k=64)'s."""
+        return self._search(lib.rfx_lex_search_deep, self.deep_workspace_bytes, (65, 1024), csr_or_texts, k, k1, b,
+                            row_mask, stream, out, workspace)
+
+    def _search(self, entry, ws_bytes, k_range, csr_or_texts, k, k1, b, row_mask, stream, out, workspace):
         if isinstance(csr_or_texts, (tuple, list)) and len(csr_or_texts) == 3 and \
                 not any(isinstance(x, str) for x in csr_or_texts):
             indptr, bucket, count = _csr(csr_or_texts)
@@ -119,11 +135,11 @@ class LexIndex:
             m, mw = row_mask, row_mask.numel()
         with self._lock, torch.cuda.device(dev):
             if workspace is None:
-                need = self.workspace_bytes(nq, k) if 1 <= nq <= 1024 and 1 <= k <= 64 else 1
+                need = ws_bytes(nq, k) if 1 <= nq <= 1024 and k_range[0] <= k <= k_range[1] else 1
                 workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-            check(lib.rfx_lex_search(self.handle, indptr.ctypes.data, bucket.ctypes.data, count.ctypes.data, nq, int(k),
-                                     float(k1), float(b), ptr(m) if m is not None else None, mw, ptr(out_s), ptr(out_r),
-                                     ptr(workspace), workspace.numel(), stream_ptr(stream)))
+            check(entry(self.handle, indptr.ctypes.data, bucket.ctypes.data, count.ctypes.data, nq, int(k),
+                        float(k1), float(b), ptr(m) if m is not None else None, mw, ptr(out_s), ptr(out_r),
+                        ptr(workspace), workspace.numel(), stream_ptr(stream)))
         return out_s, out_r
 
     # ---- fusion ----------------------------------------------------------------------------------------
@@ -133,6 +149,15 @@ class LexIndex:
         lex_rows [nq][n_l] int64 as the searches return them (rows < 0 = padding).  alpha: one float or [nq] in
         [0, 1] (1 = dense only); n_dense / n_lex: None, an int or [nq] ints = how many entries of its lists a
         question uses.  Returns (scores f32 [nq][k], rows int64 [nq][k]) and, with ranks, int32 [nq][k][2]."""
+        return self._fuse(lib.rfx_lex_fuse, dense_rows, lex_rows, k, alpha, n_dense, n_lex, rrf_c, ranks, stream, out)
+
+    def fuse_deep(self, dense_rows: torch.Tensor, lex_rows: torch.Tensor, k: int, alpha, n_dense=None, n_lex=None,
+                  rrf_c: int = DEFAULT_RRF_C, ranks: bool = False, stream=None, out=None):
+        """fuse() for lists of up to 1,024 entries and k up to 1,024 (rfx_lex_fuse_deep)."""
+        return self._fuse(lib.rfx_lex_fuse_deep, dense_rows, lex_rows, k, alpha, n_dense, n_lex, rrf_c, ranks, stream,
+                          out)
+
+    def _fuse(self, entry, dense_rows, lex_rows, k, alpha, n_dense, n_lex, rrf_c, ranks, stream, out):
         if dense_rows.dim() != 2 or lex_rows.dim() != 2 or dense_rows.shape[0] != lex_rows.shape[0]:
             raise ValueError("the lists must be [nq][n_dense] and [nq][n_lex]")
         dev = torch.device("cuda", self.device)
@@ -152,8 +177,8 @@ class LexIndex:
         else:
             out_s, out_r, out_k = out
         with torch.cuda.device(dev):
-            check(lib.rfx_lex_fuse(self.handle, ptr(dr), int(dr.shape[1]), ptr(lr), int(lr.shape[1]), nq, int(k),
-                                   al.ctypes.data, nd.ctypes.data if nd is not None else None,
-                                   nl.ctypes.data if nl is not None else None, int(rrf_c), ptr(out_s), ptr(out_r),
-                                   ptr(out_k) if out_k is not None else None, stream_ptr(stream)))
+            check(entry(self.handle, ptr(dr), int(dr.shape[1]), ptr(lr), int(lr.shape[1]), nq, int(k),
+                        al.ctypes.data, nd.ctypes.data if nd is not None else None,
+                        nl.ctypes.data if nl is not None else None, int(rrf_c), ptr(out_s), ptr(out_r),
+                        ptr(out_k) if out_k is not None else None, stream_ptr(stream)))
         return (out_s, out_r, out_k) if ranks else (out_s, out_r)

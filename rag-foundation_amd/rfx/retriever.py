@@ -145,6 +145,23 @@ def parse_hybrid(hybrid, k: int):
     return alpha, fetch_k, rrf_c, k1, b
 
 
+def parse_hybrid_deep(hybrid, k: int):
+    """parse_hybrid for candidates beyond 64: the same argument and the same rules for alpha, rrf_c,
+    k1 and b, but k <= fetch_k <= 1024 and the default fetch_k is k (reciprocal-rank fusion reads both lists at the
+    depth it answers at)."""
+    if hybrid is None:
+        return None
+    fetch_k = hybrid.get("fetch_k") if isinstance(hybrid, dict) else None
+    rest = {n: v for n, v in hybrid.items() if n != "fetch_k"} if isinstance(hybrid, dict) else hybrid
+    alpha, _, rrf_c, k1, b = parse_hybrid(rest, 1)
+    if fetch_k is not None and (isinstance(fetch_k, bool) or not isinstance(fetch_k, int)):
+        raise ValueError(f"hybrid fetch_k={fetch_k!r} must be an integer")
+    fetch_k = int(k) if fetch_k is None else int(fetch_k)
+    if not k <= fetch_k <= 1024:
+        raise ValueError(f"hybrid fetch_k={fetch_k} must satisfy k={k} <= fetch_k <= 1024")
+    return alpha, fetch_k, rrf_c, k1, b
+
+
 _DISTINCT = "\x00distinct"  # tag of a store's distinct-document batchers (no filter_key starts with NUL)
 
 
@@ -839,18 +856,25 @@ class GpuRetriever:
         hits.sort(key=lambda h: h[:3])
         return [h[3] for h in hits[:k]]
 
-    def candidates(self, store_names, question, k, metadata_filter=None):
+    def candidates(self, store_names, question, k, metadata_filter=None, hybrid=None):
         """The k best hits for 1 <= k <= 1024, rank order (score desc, store order, row asc): the candidate
         set of a stage behind the retriever (re-ranking, rank fusion, recall@100).  Up to 64 it is search();
         above, each named store answers with the deep search (LocalStore.search_deep: DeviceIndex.search_deep,
         exact, or the lists of an IVF store under RFX_IVF_DEEP=1) under its own lock and row numbering, and the
         answers are merged.  ValueError (DEEP_ERROR) on a sharded or f32 store, and on an IVF store without
-        RFX_IVF_DEEP=1."""
+        RFX_IVF_DEEP=1.
+        hybrid: as search()'s; above 64 parse_hybrid_deep's (k <= fetch_k <= 1024, default k): each store answers
+        with the reciprocal-rank fusion of its dense and its BM25 top fetch_k (flat_search_deep,
+        LexIndex.search_deep, LexIndex.fuse_deep: DESIGN §4.21), Hit.score is the fused score and several stores
+        are merged by it.  ValueError (HYBRID_ERROR) on a sharded, IVF or f32 store."""
         k = int(k)
         if not 1 <= k <= 1024:
             raise ValueError(f"k={k} out of range [1, 1024]")
         if k <= 64:
+            if hybrid is not None:
+                return self.search(store_names, question, k, metadata_filter, hybrid=hybrid)
             return self.search(store_names, question, k, metadata_filter)
+        hyb = parse_hybrid_deep(hybrid, k)
         filt = filters.check_filter(metadata_filter)
         names = list(dict.fromkeys(store_names or []))
         self.last_path = "per-store"
@@ -859,16 +883,29 @@ class GpuRetriever:
             st = self.registry.get(name)
             if st is None:
                 continue
+            if hyb and not (_diversity_ok(st) and _deep_ok(st)):
+                raise ValueError(HYBRID_ERROR)
             if not _deep_ok(st):
                 raise ValueError(DEEP_ERROR)
             if st.index.rows == 0:
                 continue
+            if hyb:
+                self.last_hybrid = "store"
 
             def run(st=st):
                 mask = st.row_mask(filt) if filt is not None else None
                 if filt is not None and mask is None:
                     return None
                 with torch.cuda.device(st.device), st.lock:  # no append moves the rows under the scan
+                    if hyb:  # one embedding and one featurisation; both searches at fetch_k, under the same mask
+                        alpha, fetch, rrf_c, k1, b = hyb
+                        lex = st.lexical()
+                        csr = featurize_texts([question], lex.V, lex.hash_seed)
+                        q = self.embedder(st.dim).embed_csr(*csr, dtype=st.dtype)
+                        _, rd = flat_search_deep(st.index, q, fetch, mask)
+                        _, rl = lex.search_deep(csr, fetch, k1=k1, b=b, row_mask=mask)
+                        s, r = lex.fuse_deep(rd, rl, k, alpha, rrf_c=rrf_c)
+                        return s[0].cpu().tolist(), r[0].cpu().tolist()
                     q = self.embedder(st.dim).embed_texts([question], st.dtype)
                     if hasattr(st, "search_deep"):  # LocalStore: the lists of an IVF store, else the flat scan
                         sel = sum(n for _, n in st.mask_ranges(filt)) if mask is not None else None
