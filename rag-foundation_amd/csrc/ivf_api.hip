@@ -17,6 +17,7 @@
 #include <mutex>
 #include <vector>
 
+#include "k_deep_select.h"
 #include "k_ivf_deep.h"
 #include "rfx_kernels.h"
 
@@ -720,7 +721,7 @@ int ivf_search_deep(rfx_ivf_t h, const void* queries_d, int64_t nq, int dtype, i
   if (rfx::ivf::launch_list_score(iv->dim, iv->nlist, L.splits, iv->lcodes, iv->linv, iv->lids, iv->off, poff, pairs, nprobe,
                                   qq, qinv, pbase, L.qcap, slab, row_mask_d, st))
     return api_fail(RFX_EUNSUPPORTED, "list score launch rejected (dim=%d)", iv->dim);
-  if (rfx::ivf::launch_deep_select(slab, L.qcap, nkeys, nq, k, out_scores_d, out_rows_d, st))
+  if (rfx::launch_deep_select(slab, L.qcap, nkeys, nq, k, out_scores_d, out_rows_d, st))
     return api_fail(RFX_EUNSUPPORTED, "deep selection rejected (k=%d)", k);
   IVF_HIP(hipGetLastError());
   return RFX_OK;
@@ -795,7 +796,7 @@ int rfx_ivf_search_deep_rerank(rfx_ivf_t h, const void* queries_d, int64_t nq, i
   IVF_HIP(hipSetDevice(iv->device));
   if (rfx::ivf::launch_rerank(queries_d, dtype, rows_d, rows_dtype, iv->dim, cr, nq, rerank_k, rs, rr, st))
     return api_fail(RFX_EUNSUPPORTED, "re-rank launch rejected");
-  if (rfx::ivf::launch_deep_order(rs, rr, nq, rerank_k, k, out_scores_d, out_rows_d, st))
+  if (rfx::launch_deep_order(rs, rr, nq, rerank_k, k, out_scores_d, out_rows_d, st))
     return api_fail(RFX_EUNSUPPORTED, "deep order rejected (k=%d)", k);
   IVF_HIP(hipGetLastError());
   return RFX_OK;

@@ -6,20 +6,20 @@
 // registers) do not reach a thousand entries; selection here is a threshold, a buffer and a periodic sort,
 // all in LDS.
 //
-// A candidate is one u64 key: (orderable f32 score << 32) | ~row.  A larger key is a better candidate under
-// the ranking rule (score desc, row asc), so one integer compare carries the tie-break through every step;
-// key 0 is "no candidate" (below the key of every real score).
+// A candidate is one u64 key, cand_key of k_cand_keys.h: a larger key is a better candidate under the ranking
+// rule (score desc, row asc), so one integer compare carries the tie-break through every step; key 0 is "no
+// candidate".
 //
 // deep_scan_kernel: grid (ranges, question groups), 256 threads.  The group's questions (16, or 8 at KB
 // 1,024) stay in registers as the B fragments of v_mfma_f32_16x16x32; each wave streams 16-row tiles of the
 // range as A fragments straight from global memory (two 16-B loads per lane and 64 columns, so a wave
 // instruction pair reads whole 128-B lines), the next tile's loads in flight under the current tile's MFMAs.
 // A lane holds 4 rows of one question: it compares them with its question's threshold (a register) and the
-// wave ballots once; only a tile with a passing row touches LDS (slots claimed by ballot + prefix count, one
-// LDS add per question and accumulator register).  Every check_rounds rounds the workgroup meets: a buffer
-// that could overflow before the next meeting is sorted (bitonic, in place, 2 * KB keys), its KB best stay
-// and the KB-th becomes the threshold.  Rows of a range arrive in ascending order between meetings, so a
-// score EQUAL to the threshold's is a worse key and is dropped by the score compare alone.
+// wave ballots once; only a tile with a passing row touches LDS (slots claimed by cand_claim: ballot + prefix
+// count, one LDS add per question and accumulator register).  Every check_rounds rounds the workgroup meets: a
+// buffer that could overflow before the next meeting is cut (cand_cut: bitonic sort in place of 2 * KB keys, its
+// KB best stay and the KB-th becomes the threshold).  Rows of a range arrive in ascending order between
+// meetings, so a score EQUAL to the threshold's is a worse key and is dropped by the score compare alone.
 //
 // deep_merge_kernel: one workgroup per question streams the ranges' lists through the same buffer routines
 // (full-key compare against the threshold), sorts, re-scores the k best by the score rule of every search

@@ -1,9 +1,10 @@
 // k_deep.hip — the deep search kernels (k_deep.h): scan with threshold + LDS buffer + periodic sort, and the
-// per-question merge with the f64 re-score.  gfx950 only.
+// per-question merge with the f64 re-score.  Keys, slot claim, sort and cut: k_cand_keys.h.  gfx950 only.
 #include "k_deep.h"
 
+#include "k_cand_keys.h"
 #include "k_mfma_common.h"
-#include "k_scan_valu.h"  // elem_rt: the score rule's element widening
+#include "k_scan_valu.h"  // rescore_dot: the score rule's f64 dot
 
 namespace rfx {
 namespace {
@@ -11,13 +12,6 @@ namespace {
 using mfc::v4f32x4;
 
 constexpr int kDeepQSlots = 16;  // threshold / count slots of a workgroup (questions per workgroup <= 16)
-
-// (score desc, row asc) as one unsigned order; s + 0 folds -0 into +0, which compare equal as floats
-__device__ __forceinline__ uint64_t deep_key(float s, int row) {
-  return ((uint64_t)ord_f32(s + 0.0f) << 32) | (uint32_t)~(uint32_t)row;
-}
-__device__ __forceinline__ float deep_key_score(uint64_t key) { return mfc::unord((uint32_t)(key >> 32)); }
-__device__ __forceinline__ int deep_key_row(uint64_t key) { return (int)~(uint32_t)key; }
 
 // LDS of a workgroup: nqg buffers of 2 * KB keys, then the thresholds (keys; 0 = none yet) and the fills.
 struct DeepBuf {
@@ -30,39 +24,6 @@ struct DeepBuf {
 };
 size_t deep_lds_bytes(int nqg, int kb) { return (size_t)nqg * 2 * kb * 8 + kDeepQSlots * 8 + kDeepQSlots * 4; }
 
-// Wave-wide (every lane calls it).  The passing lanes among `mine` (the lanes that hold this lane's question, itself
-// included) claim consecutive slots of the question's buffer: one ballot, a prefix count, one LDS add by the first
-// of them.  Returns the lane's slot, or -1.
-__device__ __forceinline__ int deep_claim(bool pass, uint64_t mine, int* cnt_q) {
-  const int lane = lane_id();
-  const uint64_t m = __ballot(pass) & mine;
-  const int leader = m ? __builtin_ctzll(m) : lane;
-  int base = 0;
-  if (pass && lane == leader) base = atomicAdd(cnt_q, __popcll(m));
-  base = __shfl(base, leader);
-  return pass ? base + __popcll(m & ((1ull << lane) - 1)) : -1;
-}
-
-// Workgroup-wide: the buffers named in `need` (uniform), n keys each (a power of two, `stride` keys apart),
-// sorted best first.  Bitonic, in place; ends on a barrier.
-__device__ __forceinline__ void deep_sort(uint64_t* buf, int stride, uint32_t need, int n) {
-  for (int k2 = 2; k2 <= n; k2 <<= 1)
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (uint32_t m = need; m; m &= m - 1) {
-        uint64_t* b = buf + (size_t)__builtin_ctz(m) * stride;
-        for (int i = threadIdx.x; i < n / 2; i += blockDim.x) {
-          const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
-          const uint64_t a = b[lo], c = b[hi];
-          if ((a < c) == ((lo & k2) == 0)) {
-            b[lo] = c;
-            b[hi] = a;
-          }
-        }
-      }
-      __syncthreads();
-    }
-}
-
 // Workgroup-wide meeting after a round of appends.  Every buffer that holds more than `lim` keys is sorted, its
 // KB best stay and the KB-th becomes its threshold (lim = -1: every buffer, the final cut).  Returns the buffers
 // it cut (uniform).  Nothing may be appended between the entry and the return.
@@ -73,17 +34,7 @@ __device__ __forceinline__ uint32_t deep_compact(const DeepBuf& B, int nqg, int 
   for (int q = 0; q < nqg; ++q) need |= (B.cnt[q] > lim ? 1u : 0u) << q;
   __syncthreads();  // every thread has read the fills before anyone appends again
   if (!need) return 0;
-  for (uint32_t m = need; m; m &= m - 1) {
-    const int q = __builtin_ctz(m);
-    for (int i = min(B.cnt[q], N) + (int)threadIdx.x; i < N; i += blockDim.x) B.buf[(size_t)q * N + i] = 0;
-  }
-  __syncthreads();
-  deep_sort(B.buf, N, need, N);
-  if ((int)threadIdx.x < nqg && ((need >> threadIdx.x) & 1u)) {
-    B.cnt[threadIdx.x] = min(B.cnt[threadIdx.x], B.KB);
-    B.tau[threadIdx.x] = B.buf[(size_t)threadIdx.x * N + B.KB - 1];
-  }
-  __syncthreads();
+  cand_cut(B.buf, N, B.KB, need, B.cnt, B.tau);
   return need;
 }
 
@@ -137,8 +88,8 @@ __device__ __forceinline__ void deep_use_tile(const uint4 (&a)[2 * NDS], uint32_
   const uint64_t mine = 0x0001000100010001ull << n;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
-    const int slot = deep_claim(p[i], mine, &B.cnt[n]);
-    if (slot >= 0 && slot < N) B.buf[(size_t)n * N + slot] = deep_key(acc[i], r0 + 4 * g + i);
+    const int slot = cand_claim(p[i], mine, &B.cnt[n]);
+    if (slot >= 0 && slot < N) B.buf[(size_t)n * N + slot] = cand_key(acc[i], r0 + 4 * g + i);
   }
 }
 
@@ -198,7 +149,7 @@ __global__ __launch_bounds__(kDeepThreads) void deep_scan_kernel(const uint8_t* 
     // (check_rounds is even: a meeting falls after the second tile of a pair)
     if ((t + 2) % P.check_rounds == 0 && deep_compact(B, QG, lim) && qlive) {
       const uint64_t tk = B.tau[n];
-      thr = tk ? deep_key_score(tk) : -__builtin_inff();
+      thr = tk ? cand_key_score(tk) : -__builtin_inff();
     }
   }
   deep_compact(B, QG, -1);
@@ -230,36 +181,26 @@ __global__ __launch_bounds__(kDeepThreads) void deep_merge_kernel(const uint64_t
     const int i = base + tid;
     const uint64_t key = tid < R && i < total ? src[i] : 0;
     const bool pass = key > B.tau[0];  // the full key: equal scores of different ranges go to the lower row
-    const int slot = deep_claim(pass, ~0ull, &B.cnt[0]);
+    const int slot = cand_claim(pass, ~0ull, &B.cnt[0]);
     if (slot >= 0 && slot < N) B.buf[slot] = key;
     deep_compact(B, 1, lim);
   }
   deep_compact(B, 1, -1);  // buf[0 .. KB): the best, in order; empty places (key 0) last
 
-  // the score rule of every search: fl32 of the f64 dot of the stored values (8 lanes per entry, the
-  // summation order of rescore_final), then the order again under the new scores
+  // the score rule of every search: fl32 of the f64 dot of the stored values (8 lanes per entry), then the
+  // order again under the new scores
   const int gl = tid & 7;
   for (int e0 = 0; e0 < KB; e0 += kDeepThreads / 8) {
     const int e = e0 + (tid >> 3);
     const uint64_t key = e < k ? B.buf[e] : 0;
-    int row = key ? deep_key_row(key) : -1;
+    int row = key ? cand_key_row(key) : -1;
     if (row >= nrows) row = -1;
-    double acc = 0.0;
-    if (row >= 0) {
-      const int64_t xr = (int64_t)row * D, qr = q * D;
-      for (int c = gl; c < D; c += 8) acc += (double)elem_rt(X, xr + c, dtype) * (double)elem_rt(Q, qr + c, dtype);
-    }
-#pragma unroll
-    for (int off = 4; off; off >>= 1) acc += __shfl_xor(acc, off);
-    if (gl == 0) B.buf[KB + e] = row >= 0 ? deep_key((float)acc, row) : 0;
+    const double acc = rescore_dot(X, row, Q, q, D, dtype, gl, row >= 0);
+    if (gl == 0) B.buf[KB + e] = row >= 0 ? cand_key((float)acc, row) : 0;
   }
   __syncthreads();
-  deep_sort(B.buf + KB, KB, 1u, KB);
-  for (int j = tid; j < k; j += kDeepThreads) {
-    const uint64_t key = B.buf[KB + j];
-    out_s[q * k + j] = key ? deep_key_score(key) : -__builtin_inff();
-    out_r[q * k + j] = key ? (int64_t)deep_key_row(key) : -1;
-  }
+  cand_sort(B.buf + KB, KB, 1u, KB);
+  cand_write(B.buf + KB, q, k, out_s, out_r);
 }
 
 template <int DT, int NDS>

@@ -1,12 +1,13 @@
 // k_deep_sampled.hip — the sampled-threshold deep search (k_deep_sampled.h): the staged scan with its DENSE and
 // THRESH epilogues, the small kernels between the passes, and the call that strings them together with the
-// selection of k_ivf_deep.h and the fallback to k_deep.h.  gfx950 only.
+// selection of k_deep_select.h and the fallback to k_deep.h.  Keys: k_cand_keys.h.  gfx950 only.
 #include "k_deep_sampled.h"
 
+#include "k_cand_keys.h"
 #include "k_deep.h"
-#include "k_ivf_deep.h"
+#include "k_deep_select.h"
 #include "k_mfma_common.h"
-#include "k_scan_valu.h"  // elem_rt: the score rule's element widening
+#include "k_scan_valu.h"  // rescore_dot: the score rule's f64 dot
 
 namespace rfx {
 namespace {
@@ -19,11 +20,6 @@ constexpr int kDsChunks = kDsStage / 16;       // 16-B chunks of a stage
 constexpr int kDsTiles = kDsRound / 16;
 
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
-
-// cand_key of k_deep / k_ivf_deep: (score desc, row asc) as one unsigned order; s + 0 folds -0 into +0
-__device__ __forceinline__ uint64_t ds_key(float s, int row) {
-  return ((uint64_t)ord_f32(s + 0.0f) << 32) | (uint32_t)~(uint32_t)row;
-}
 
 struct DsScan {
   const uint8_t* X;
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && NDS >= 12) ? 1 : 2) void
           uint64_t key[4];
 #pragma unroll
           for (int i = 0; i < 4; ++i)
-            key[i] = ((nb >> i) & 1u) && acc[t][i] == acc[t][i] ? ds_key(acc[t][i], (o0 + i) * a.stride) : 0ull;
+            key[i] = ((nb >> i) & 1u) && acc[t][i] == acc[t][i] ? cand_key(acc[t][i], (o0 + i) * a.stride) : 0ull;
           uint64_t* dst = a.slab + (int64_t)q * a.slab_stride + o0;  // 16-B aligned: the stride is even, o0 % 4 == 0
           if (o0 + 3 < o_hi) {
             ((u64x2*)dst)[0] = u64x2{key[0], key[1]};
@@ -181,7 +177,7 @@ __global__ __launch_bounds__(64 * WAVES, (WAVES == 4 && NDS >= 12) ? 1 : 2) void
         for (int i = 0; i < 4; ++i)
           if (p[i]) {
             const int at = atomicAdd(a.count + q, 1);
-            if (at < a.cap) a.slab[(int64_t)q * a.slab_stride + at] = ds_key(acc[t][i], o0 + i);
+            if (at < a.cap) a.slab[(int64_t)q * a.slab_stride + at] = cand_key(acc[t][i], o0 + i);
           }
       }
     }
@@ -222,7 +218,7 @@ __global__ __launch_bounds__(1024) void ds_close_kernel(const int* __restrict__ 
 }
 
 // The score rule of every search on the selected rows: fl32 of the f64 dot of the stored values, 8 lanes per
-// row in rescore_final's summation order (deep_merge_kernel's loop).  Block = question; sel_r < 0: no row.
+// row (rescore_dot).  Block = question; sel_r < 0: no row.
 __global__ __launch_bounds__(256) void ds_rescore_kernel(const void* __restrict__ X, int nrows, int D, int dtype,
                                                          const void* __restrict__ Q, const int64_t* __restrict__ sel_r, int k,
                                                          float* __restrict__ rs_s) {
@@ -232,13 +228,7 @@ __global__ __launch_bounds__(256) void ds_rescore_kernel(const void* __restrict_
     const int e = e0 + (threadIdx.x >> 3);
     int64_t row = e < k ? sel_r[q * k + e] : -1;
     if (row >= nrows) row = -1;
-    double acc = 0.0;
-    if (row >= 0) {
-      const int64_t xr = row * D, qr = q * D;
-      for (int c = gl; c < D; c += 8) acc += (double)elem_rt(X, xr + c, dtype) * (double)elem_rt(Q, qr + c, dtype);
-    }
-#pragma unroll
-    for (int off = 4; off; off >>= 1) acc += __shfl_xor(acc, off);
+    const double acc = rescore_dot(X, row, Q, q, D, dtype, gl, row >= 0);
     if (gl == 0 && e < k) rs_s[q * k + e] = row >= 0 ? (float)acc : -__builtin_inff();
   }
 }
@@ -320,7 +310,7 @@ int launch_deep_sampled_search(const DeepSampledPlan& p, const void* X, int64_t 
     a.n_ord = p.S, a.stride = p.stride, a.thresh = 0;
     if (launch_scan(a, dtype, p, st)) return -1;
     hipLaunchKernelGGL(ds_close_kernel, dim3(1), dim3(1024), 0, st, count, nqi, p.S, 1, p.S, n_keys, fb_list, head);
-    if (ivf::launch_deep_select(slab, p.slab, n_keys, nq, k, sel_s, sel_r, st)) return -1;
+    if (launch_deep_select(slab, p.slab, n_keys, nq, k, sel_s, sel_r, st)) return -1;
     hipLaunchKernelGGL(ds_tau_kernel, dim3((unsigned)((nqi + 255) / 256)), dim3(256), 0, st, sel_s, k, nqi, tau, count);
   }
   // 2. the main pass over every row
@@ -328,9 +318,9 @@ int launch_deep_sampled_search(const DeepSampledPlan& p, const void* X, int64_t 
   if (nrows > 0 && launch_scan(a, dtype, p, st)) return -1;
   hipLaunchKernelGGL(ds_close_kernel, dim3(1), dim3(1024), 0, st, count, nqi, p.cap, p.dense, (int)nrows, n_keys, fb_list, head);
   // 3. the k best by (MFMA score desc, row asc), re-scored by the score rule, ordered again
-  if (ivf::launch_deep_select(slab, p.slab, n_keys, nq, k, sel_s, sel_r, st)) return -1;
+  if (launch_deep_select(slab, p.slab, n_keys, nq, k, sel_s, sel_r, st)) return -1;
   hipLaunchKernelGGL(ds_rescore_kernel, dim3((unsigned)nq), dim3(256), 0, st, X, (int)nrows, D, dtype, Q, sel_r, k, rs_s);
-  if (ivf::launch_deep_order(rs_s, sel_r, nq, k, k, out_s, out_r, st)) return -1;
+  if (launch_deep_order(rs_s, sel_r, nq, k, k, out_s, out_r, st)) return -1;
   if (p.dense) return 0;  // a DENSE pass cannot overflow
   // 4. the questions whose slab overflowed: the deep search of k_deep.h over a compact copy, scattered back
   uint4* fb_q = (uint4*)(ws + w.fb_q);

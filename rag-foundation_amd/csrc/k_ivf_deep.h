@@ -5,9 +5,8 @@
 // score is written once and each question's k best are selected afterwards: two kernels, nothing in the scan
 // waits on a sort.
 //
-// A candidate is one u64 key, as in k_deep.h: (ord_f32(score + 0.0f) << 32) | ~row.  A larger key is a better
-// candidate under (score desc, row asc); key 0 is "none" (an ineligible row).  The output score is decoded from
-// the key, so a -0.0 score is reported as +0.0.
+// A candidate is one u64 key, cand_key of k_cand_keys.h; key 0 is an ineligible row.  The output score is decoded
+// from the key, so a -0.0 score is reported as +0.0.
 //
 // Slab: question q owns slab[q * qcap, (q + 1) * qcap).  Its probe slot j (pair p = q * nprobe + j) owns the
 // run [pair_base[p], pair_base[p] + rows of the probed list), pair_base the exclusive prefix of the probed
@@ -19,10 +18,7 @@
 // through scalar loads into v_dot4) without the top-k lists: per staged pair the lane stores its row's key, a
 // wave's store one 512-B run.
 //
-// deep_select_kernel: one workgroup of 1,024 threads per question.  Most-significant-first radix passes of 8 bits
-// over the key (256-bin histogram, suffix scan, the bin of the k-th key extends the prefix) until the keys above
-// the prefix and in its bin number at most 2 * KB; those are gathered into LDS, sorted (bitonic, 2 * KB keys)
-// and the k best written.  deep_order_kernel: the same sort over the re-ranked candidates of a question.
+// The selection (each question's k best of its slab) and the order of the re-ranked candidates: k_deep_select.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -62,12 +58,5 @@ void launch_pair_base(const int64_t* pid, const int64_t* off, int64_t nq, int np
 int launch_list_score(int D, int m, int splits, const int8_t* codes, const float* inv, const int* ids, const int64_t* off,
                       const int* pair_off, const int* pairs, int nprobe, const int8_t* qq, const float* qinv,
                       const int* pair_base, int64_t qcap, uint64_t* slab, const uint32_t* row_mask, hipStream_t st);
-// each question's k best keys (65 <= k <= 1,024) -> out_s / out_r [nq][k], padded (-inf, -1)
-int launch_deep_select(const uint64_t* slab, int64_t qcap, const int* n_keys, int64_t nq, int k, float* out_s,
-                       int64_t* out_r, hipStream_t st);
-// s / r [nq][n] (n <= 1,024; r < 0 or a NaN score: no candidate) -> the k <= n best by (score desc, row asc)
-int launch_deep_order(const float* s, const int64_t* r, int64_t nq, int n, int k, float* out_s, int64_t* out_r,
-                      hipStream_t st);
-
 }  // namespace ivf
 }  // namespace rfx

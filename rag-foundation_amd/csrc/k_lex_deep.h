@@ -3,8 +3,7 @@
 //
 // Path: the retrieval slice of ask_stream (gemini_rag.py:517-551) at the depth a rank fusion or a re-ranker reads.
 //
-// A candidate is one u64 key, as in k_deep.h / k_ivf_deep.h: (ord_f32(score) << 32) | ~row.  A larger key is a
-// better candidate under (score desc, row asc); key 0 is "none" (a BM25 score that ranks is > 0).
+// A candidate is one u64 key, cand_key of k_cand_keys.h; a BM25 score that ranks is > 0, so its key is never 0.
 //
 // lex_deep_scan_kernel<NQT, LDS>: grid (blocks, groups), 1,024 threads, lex_scan_kernel's tile walk.  A group is
 // 4 questions (1 for a lone question): the weight table w[V][4] takes 64 KB at V 4,096 and leaves LDS for the
@@ -14,7 +13,7 @@
 // at most kLexDeepRound = 512 keys to a buffer; it meets after every round and cuts every buffer whose fill has
 // passed CAP - 512 (sort, keep KB, tau = the KB-th key).  A buffer therefore starts every round with room for
 // the whole round: it cannot overflow, and there is no other path.  At the end each buffer is cut once more and
-// its KB keys go to slab[q][block * KB ..); ivf::launch_deep_select picks each question's k best of them.
+// its KB keys go to slab[q][block * KB ..); launch_deep_select (k_deep_select.h) picks each question's k best of them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

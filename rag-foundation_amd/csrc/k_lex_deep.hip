@@ -1,50 +1,14 @@
 // k_lex_deep.hip — the deep BM25 scan kernel and its launchers (see k_lex_deep.h; rules: DESIGN §4.14, §4.21).
 #include "k_lex_deep.h"
 
+#include "k_cand_keys.h"
 #include "k_lex_score.h"
-#include "rfx_device.h"
 
 namespace rfx {
 namespace {
 
 constexpr int kLexWaves = kLexThreads / kWave;
 static_assert(kLexWaves * 32 == kLexDeepRound, "a round is one 32-row tile per wave");
-
-// (score desc, row asc) as one unsigned order; a ranking score is > 0, so the key is never 0
-__device__ __forceinline__ uint64_t lex_key(float s, int row) {
-  return ((uint64_t)ord_f32(s) << 32) | (uint32_t)~(uint32_t)row;
-}
-
-// Workgroup-wide bitonic sort of b[0 .. n) (n a power of two >= 2), largest key first.  The caller's writes are
-// behind a barrier, and it ends on one.
-__device__ __forceinline__ void sort_keys_desc(uint64_t* b, int n) {
-  for (int k2 = 2; k2 <= n; k2 <<= 1)
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < n / 2; i += kLexThreads) {
-        const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
-        const uint64_t a = b[lo], c = b[hi];
-        if ((a < c) == ((lo & k2) == 0)) {
-          b[lo] = c;
-          b[hi] = a;
-        }
-      }
-      __syncthreads();
-    }
-}
-
-// The cut of one buffer, by the whole workgroup (every wave is here: nothing is appended meanwhile): pad with
-// key 0, sort, keep the kb best, tau <- the kb-th key (0 while fewer are held).
-__device__ __forceinline__ void cut_buffer(uint64_t* b, int cap, int kb, int* fill, uint64_t* tau) {
-  const int n = min(*fill, cap);
-  for (int i = n + threadIdx.x; i < cap; i += kLexThreads) b[i] = 0;
-  __syncthreads();
-  sort_keys_desc(b, cap);
-  if (threadIdx.x == 0) {
-    *tau = b[kb - 1];
-    *fill = min(n, kb);
-  }
-  __syncthreads();
-}
 
 template <int NQT, bool LDS>
 __global__ __launch_bounds__(kLexThreads) void lex_deep_scan_kernel(
@@ -116,7 +80,7 @@ __global__ __launch_bounds__(kLexThreads) void lex_deep_scan_kernel(
           lex_accumulate<NQT>(ent[u], B, k1p1, wt, acc);
           for (long long i = s[u] + 64 + lane; i < e[u]; i += 64) lex_accumulate<NQT>(entries[i], B, k1p1, wt, acc);
           const double sum = lex_reduce<NQT>(acc, lane);
-          const uint64_t key = lex_key((float)sum, (int)(r0 + rj[u]));
+          const uint64_t key = cand_key((float)sum, (int)(r0 + rj[u]));
 #pragma unroll
           for (int q = 0; q < NQT; ++q)
             if (lane == lex_owner_lane<NQT>(q) && sum > 0.0 && key > s_tau[q]) {
@@ -131,17 +95,17 @@ __global__ __launch_bounds__(kLexThreads) void lex_deep_scan_kernel(
     if (s_cut[par]) {    // workgroup-uniform: this round's flag is written again two rounds on at the earliest
       __syncthreads();   // every thread has read it
       if (tid == 0) s_cut[par] = 0;
+      uint32_t need = 0;
 #pragma unroll
-      for (int q = 0; q < NQT; ++q)
-        if (s_fill[q] > limit) cut_buffer(buf + (size_t)q * cap, cap, kb, &s_fill[q], &s_tau[q]);
+      for (int q = 0; q < NQT; ++q) need |= (s_fill[q] > limit ? 1u : 0u) << q;
+      cand_cut(buf, cap, kb, need, s_fill, s_tau);
     }
   }
   // ---- the block's kb best of every question -> its run of the slab ------------------------------------------
-#pragma unroll
-  for (int q = 0; q < NQT; ++q) {
+  const int nlive = (int)max((int64_t)0, min((int64_t)NQT, nq - (int64_t)g * NQT));  // the group's questions (uniform)
+  cand_cut(buf, cap, kb, (1u << nlive) - 1u, s_fill, s_tau);
+  for (int q = 0; q < nlive; ++q) {
     const int64_t gq = (int64_t)g * NQT + q;
-    if (gq >= nq) break;  // uniform
-    cut_buffer(buf + (size_t)q * cap, cap, kb, &s_fill[q], &s_tau[q]);
     uint64_t* run = slab + ((size_t)gq * gridDim.x + blockIdx.x) * kb;
     for (int i = tid; i < kb; i += kLexThreads) run[i] = buf[(size_t)q * cap + i];
     if (blockIdx.x == 0 && tid == 0) n_keys[gq] = (int)gridDim.x * kb;

@@ -35,13 +35,8 @@ __device__ __forceinline__ v4f32x4 mfma16(const uint4& a, const uint4& b, const 
                                                   0, 0, 0);
 }
 
-__device__ __forceinline__ uint32_t ord(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float unord(uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
+__device__ __forceinline__ uint32_t ord(float f) { return ord_f32(f); }
+__device__ __forceinline__ float unord(uint32_t o) { return unord_f32(o); }
 // NaN-ignoring 3-way max.  Plain fmaxf (hipcc emits v_max3_f32): an inline-asm v_max3 reading an
 // MFMA accumulator gets no MFMA->VALU wait states from hipcc and can read it before the MFMA has
 // written it (measured: rows of a tile's first 8 accumulator registers lost, k_scan_mfma5.h).

@@ -46,9 +46,6 @@ __device__ __forceinline__ uint32_t ord32(float f) {
   const uint32_t b = __float_as_uint(f);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
-__device__ __forceinline__ float unord32(uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
 __device__ __forceinline__ uint64_t mkkey(float s, int row) {
   return ((uint64_t)ord32(s) << 32) | (uint32_t)(~(uint32_t)row);
 }
@@ -297,7 +294,7 @@ __global__ __launch_bounds__(512) void scan_mfma2_kernel(const uint16_t* __restr
 #pragma unroll
       for (int i = 0; i < KL; ++i) {
         const uint64_t key = L[n][i];
-        cand_s[o + i] = key ? unord32((uint32_t)(key >> 32)) : -__builtin_inff();
+        cand_s[o + i] = key ? unord_f32((uint32_t)(key >> 32)) : -__builtin_inff();
         cand_r[o + i] = key ? (int)(~(uint32_t)key) : kEmptyRow;
       }
     }

@@ -51,9 +51,6 @@ __device__ __forceinline__ uint32_t ord3(float f) {
   const uint32_t b = __float_as_uint(f);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
-__device__ __forceinline__ float unord3(uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
 // NaN-ignoring 3-way max as plain fmaxf (hipcc emits v_max3_f32 and pads the MFMA->VALU hazard an
 // inline-asm reader of an accumulator would not get).
 __device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
@@ -231,7 +228,7 @@ __global__ __launch_bounds__(256, 1) void scan_mfma3_kernel(const uint16_t* __re
     const uint32_t shared_o = *(const uint32_t*)(lds + k3TauOff + (w * k3QW + l32) * 4);
     const uint32_t own_o = (uint32_t)(L[KL - 1] >> 32);
     const uint32_t thr_o = own_o > shared_o ? own_o : shared_o;
-    const float thr = thr_o ? unord3(thr_o) : -__builtin_inff();
+    const float thr = thr_o ? unord_f32(thr_o) : -__builtin_inff();
     if (mx >= thr) {
 #pragma unroll
       for (int m = 0; m < 4; ++m)
@@ -258,7 +255,7 @@ __global__ __launch_bounds__(256, 1) void scan_mfma3_kernel(const uint16_t* __re
 #pragma unroll
     for (int i = 0; i < KL; ++i) {
       const uint64_t key = L[i];
-      cand_s[o + i] = key ? unord3((uint32_t)(key >> 32)) : -__builtin_inff();
+      cand_s[o + i] = key ? unord_f32((uint32_t)(key >> 32)) : -__builtin_inff();
       cand_r[o + i] = key ? (int)(~(uint32_t)key) : kEmptyRow;
     }
   }

@@ -122,6 +122,22 @@ __device__ __forceinline__ float elem_rt(const void* p, int64_t i, int dtype) {
   return dtype == RFX_BF16 ? bf16_to_f32(h) : f16_to_f32(h);
 }
 
+// The f64 dot of the rule above, by 8 adjacent lanes per entry (gl = the lane's place among them; all 8 call it,
+// `live` the same in each): row `row` of X against row q of Q, D elements each, lane gl the columns gl, gl + 8,
+// ..., then the 8 partial sums by xor 4, 2, 1.  This order of summation defines the returned score bits: it is
+// rescore_final's below, which keeps its own loop (its kernels' code is pinned).  Not live: 0, nothing is read.
+__device__ __forceinline__ double rescore_dot(const void* X, int64_t row, const void* Q, int64_t q, int D, int dtype,
+                                              int gl, bool live) {
+  double acc = 0.0;
+  if (live) {
+    const int64_t xr = row * D, qr = q * D;
+    for (int c = gl; c < D; c += 8) acc += (double)elem_rt(X, xr + c, dtype) * (double)elem_rt(Q, qr + c, dtype);
+  }
+#pragma unroll
+  for (int off = 4; off; off >>= 1) acc += __shfl_xor(acc, off);
+  return acc;
+}
+
 // Block-wide (any block size that is a multiple of 64, k_out <= 64): the k_out entries just written
 // for query q (out_s / out_r, or out_rec; the merge added row_offset to the rows in both forms, so the
 // row of X is row - row_offset either way) re-scored and re-ordered by the rule above.  The caller's
@@ -677,10 +693,7 @@ __device__ __forceinline__ void merge_one(const Src& src, int64_t q, int list_le
   }
   if (lane == 0 && m) atomicMax(&tb, m);
   __syncthreads();
-  if (tb) {
-    const uint32_t u = tb & 0x80000000u ? tb & 0x7fffffffu : ~tb;  // inverse of ord_f32
-    L.init_above(__uint_as_float(u), kNoRow);                      // admits score >= T
-  }
+  if (tb) L.init_above(unord_f32(tb), kNoRow);  // admits score >= T
   if constexpr (SORTED) {
     // lane walks list lb + lane while its entries still beat the wave list's admission bound
     // (wave-uniform; it only rises): a sorted list's later entries cannot do better

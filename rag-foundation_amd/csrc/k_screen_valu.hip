@@ -83,10 +83,6 @@ __device__ __forceinline__ float f32_up(double v) {
   return f;
 }
 
-__device__ __forceinline__ float unord_f32(uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-
 // D / 16 bytes of int8 codes per lane of a 16-lane row group: chunk c = j + 16 i (16 B each)
 template <int D>
 struct Codes {
@@ -988,8 +984,7 @@ __global__ __launch_bounds__(256) void screen_valu_kernel(const int8_t* __restri
 #pragma unroll 8
         for (int f = 0; f < ns; ++f) rank += skey[f] > ke ? 1 : 0;
         if (rank < k_out) {
-          const uint32_t o = (uint32_t)(ke >> 32);
-          out_s[(int64_t)qi * k_out + rank] = __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+          out_s[(int64_t)qi * k_out + rank] = unord_f32((uint32_t)(ke >> 32));
           out_r[(int64_t)qi * k_out + rank] = (int)(~(uint32_t)ke);
         }
       }

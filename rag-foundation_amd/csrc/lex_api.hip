@@ -14,9 +14,9 @@
 #include <mutex>
 #include <vector>
 
+#include "k_deep_select.h"
 #include "k_fuse.h"
 #include "k_fuse_deep.h"
-#include "k_ivf_deep.h"
 #include "k_lex.h"
 #include "k_lex_deep.h"
 #include "rfx_kernels.h"
@@ -440,7 +440,7 @@ int rfx_lex_search_deep(rfx_lex_t h, const int32_t* q_indptr_h, const int32_t* q
   if (rfx::launch_lex_deep_scan(W.p, H.V, lx->indptr, lx->entries, lx->len, H.rows, (const float*)(w8 + W.w_off), nq,
                                 (double)k1, (double)b, H.avgdl(), mask_d, slab, n_keys, st) != 0)
     return api_fail(RFX_EUNSUPPORTED, "lex deep scan launch rejected");
-  if (rfx::ivf::launch_deep_select(slab, (int64_t)W.p.blocks * W.p.kb, n_keys, nq, k, scores_d, rows_d, st) != 0)
+  if (rfx::launch_deep_select(slab, (int64_t)W.p.blocks * W.p.kb, n_keys, nq, k, scores_d, rows_d, st) != 0)
     return api_fail(RFX_EUNSUPPORTED, "lex deep search: selection k=%d unsupported", k);
   LEX_HIP(hipGetLastError());
   return RFX_OK;

@@ -23,6 +23,10 @@ __device__ __forceinline__ uint32_t ord_f32(float s) {
   const uint32_t u = __float_as_uint(s);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+// its inverse: the float of an ord_f32 key
+__device__ __forceinline__ float unord_f32(uint32_t o) {
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
 
 // ---- row masks (metadata filters): bit (r & 31) of word r >> 5 set = row r may be returned ------
 // A lane of a 32x32 MFMA accumulator holds rows rb + (r & 3) + 8 (r >> 2), r < 16, with
