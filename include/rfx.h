@@ -294,6 +294,31 @@ int rfx_search_deep_sampled(rfx_index_t h, const void* queries_d, int64_t nq, in
  * sample: S = 0); else the sample is the S rows i * stride and a question's slab takes cap keys in the main pass.
  * Same errors as rfx_search_deep. */
 int rfx_deep_sampled_plan(int64_t rows, int dim, int dtype, int64_t nq, int k, int* out /* [6] */);
+/* Diversified retrieval at depth: rfx_mmr_select's rule, word for word — sim, step 0, the objective
+ * in f64 with every operation rounded on its own, ties to the lower position, padding, the (-inf, -1) tail, prefix
+ * stability, lambda = 1 the identity, an answer independent of its batch — over n_cand_max in 65..1024 candidates
+ * per query and k in 1..n_cand_max (k may exceed 64): the pool of a diversified answer at the depth of
+ * rfx_search_deep, or the candidate set of a re-ranker behind the retrieval slice of ask_stream
+ * (gemini_rag.py:517-551).  The argument list is rfx_mmr_select's; the candidates are the answer of
+ * rfx_search_deep (or any list in that form) on this index.  Two launches per slice of the batch (a slice keeps
+ * its similarity matrices at or under 512 MiB: 128 queries at 1024 candidates), stream-ordered, no host wait: an
+ * approximate similarity matrix per query on the matrix cores under a proven error bound, then the selection,
+ * which takes the exact f64 dot only where the bound cannot decide.  ws_d: 256-byte aligned,
+ * rfx_mmr_deep_workspace_bytes; after the call its first 2 * nq int32 hold per query the contenders summed over
+ * the steps and the exact dots taken.  RFX_EINVAL before anything is enqueued: n_cand_max outside 65..1024, k
+ * outside 1..n_cand_max, nq outside 1..1024, a lambda outside [0, 1] or NaN, an n_cand_h entry outside
+ * 1..n_cand_max, null candidates or outputs, a workspace too small or unaligned.  RFX_EUNSUPPORTED: an f32 store,
+ * dim not a multiple of 64 or above 1024.  Union views are served as rfx_mmr_select serves them. */
+int rfx_mmr_deep_workspace_bytes(rfx_index_t h, int64_t nq, int n_cand_max, size_t* out_bytes);
+/* Host only (no device call): the plan rfx_mmr_select_deep would use.  out[5] = {n_pad (n_cand_max rounded up to
+ * the 64-candidate tile), tile pairs of the upper triangle (the Gram grid per query), queries per slice, slices,
+ * workspace bytes}.  RFX_EINVAL as rfx_mmr_select_deep for nq and n_cand_max. */
+int rfx_mmr_deep_plan(int64_t nq, int n_cand_max, int64_t* out /* [5] */);
+int rfx_mmr_select_deep(rfx_index_t h, const void* queries_d, int64_t nq, int n_cand_max, int k,
+                        const float* lambda_h, const int32_t* n_cand_h,      /* [nq] host; NULL = 0.5 / n_cand_max */
+                        const float* cand_scores_d, const int64_t* cand_rows_d, /* [nq][n_cand_max] */
+                        float* out_scores_d, int64_t* out_rows_d, float* out_obj_d /* may be NULL */,
+                        void* ws_d, size_t ws_bytes, void* stream);
 /* Merge per-query candidate lists into the final top-k.  rows are int32 (rows_are_i64 = 0) or
  * int64 (1); row_offset is added to every returned row (shard base for multi-GPU). */
 int rfx_topk_merge(const float* cand_scores_d, const void* cand_rows_d, int rows_are_i64,

@@ -23,4 +23,10 @@ struct IndexRead {
 // reader lock timed out) with rfx_last_error set.
 int api_index_read(rfx_index_t h, IndexRead* out);
 
+// `bytes` of per-question tables to dst_d on stream st through the index's pinned staging buffer, as
+// rfx_search_segmented stages its tables: fill(stage, ctx) writes them on the host, the caller's arrays may die on
+// return and the copy stays stream-ordered.  RFX_OK, or RFX_ENOMEM / RFX_EDEVICE with rfx_last_error set.
+int api_stage_tables(const IndexRead& ix, size_t bytes, void (*fill)(uint8_t* stage, void* ctx), void* ctx, void* dst_d,
+                     void* st);
+
 }  // namespace rfx

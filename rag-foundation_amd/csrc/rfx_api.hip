@@ -847,6 +847,27 @@ int api_index_read(rfx_index_t h, IndexRead* out) {
   out->keep = ix;
   return RFX_OK;
 }
+
+int api_stage_tables(const IndexRead& r, size_t bytes, void (*fill)(uint8_t* stage, void* ctx), void* ctx, void* dst_d,
+                     void* st) {
+  Index* ix = (Index*)r.keep.get();
+  std::lock_guard<std::mutex> slk(ix->seg_mu);
+  if (!ix->seg_ev) RFX_HIP(hipEventCreateWithFlags(&ix->seg_ev, hipEventDisableTiming));
+  else RFX_HIP(hipEventSynchronize(ix->seg_ev));  // the copy of the call before has left the buffer
+  if (ix->seg_stage_bytes < bytes) {
+    if (ix->seg_stage) RFX_HIP(hipHostFree(ix->seg_stage));
+    ix->seg_stage = nullptr;
+    ix->seg_stage_bytes = 0;
+    const size_t want = std::max(bytes * 2, (size_t)1 << 16);
+    if (hipHostMalloc(&ix->seg_stage, want, hipHostMallocDefault) != hipSuccess)
+      return fail(RFX_ENOMEM, "hipHostMalloc(%zu) failed (staged tables)", want);
+    ix->seg_stage_bytes = want;
+  }
+  fill((uint8_t*)ix->seg_stage, ctx);
+  RFX_HIP(hipMemcpyAsync(dst_d, ix->seg_stage, bytes, hipMemcpyHostToDevice, (hipStream_t)st));
+  RFX_HIP(hipEventRecord(ix->seg_ev, (hipStream_t)st));
+  return RFX_OK;
+}
 }  // namespace rfx
 
 extern "C" {

@@ -163,8 +163,8 @@ class LocalGpuRag:
         """Top-k hits.  k: the request's top_k (the reference route drops it,
         chat.py:66), default self.top_k; 1..64.  top_k (keyword; in place of k): 1..1024 — above 64 the hits are
         GpuRetriever.candidates' (the deep search: flat bf16 / f16 stores, IVF ones under RFX_IVF_DEEP=1; hybrid as
-        below, fused at depth on flat stores; no diversity or distinct; what a re-ranking stage reads), up to 64
-        the same as k.  diversity: a lambda in [0, 1] or {"lambda": ..,
+        below, fused at depth on flat stores; a diversity given in the call is candidates' deep MMR, the
+        RFX_MMR_LAMBDA default does not apply; no distinct; what a re-ranking stage reads), up to 64 the same as k.  diversity: a lambda in [0, 1] or {"lambda": ..,
         "fetch_k": ..} picks the k hits by MMR from the fetch_k best (GpuRetriever.search); None = the
         default of RFX_MMR_LAMBDA (unset: off).  hybrid: an alpha in [0, 1] or {"alpha", "fetch_k", "rrf_c",
         "k1", "b"} fuses the dense answer with the BM25 answer over the chunk texts (GpuRetriever.search;
@@ -177,6 +177,8 @@ class LocalGpuRag:
             if int(top_k) > 64:
                 hyb = self.hybrid if hybrid is None else hybrid
                 kw = {} if hyb is None else {"hybrid": hyb}
+                if diversity is not None:  # the request's own, never the RFX_MMR_LAMBDA default
+                    kw["diversity"] = diversity
                 return self.retriever.candidates(list(store_names or []), question, int(top_k), metadata_filter=filt,
                                                  **kw)
             k = int(top_k)

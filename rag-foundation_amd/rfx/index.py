@@ -339,6 +339,54 @@ class DeviceIndex:
         s, r = self.search(queries, int(fetch_k), row_mask=row_mask)
         return self.mmr_select(queries, s, r, int(k), lam=lam)
 
+    # ---- diversified retrieval at depth (MMR over 65..1,024 candidates) -----------------
+    def mmr_deep_workspace_bytes(self, nq: int, n_cand_max: int) -> int:
+        b = ctypes.c_size_t()
+        check(lib.rfx_mmr_deep_workspace_bytes(self.handle, int(nq), int(n_cand_max), ctypes.byref(b)))
+        return b.value
+
+    def mmr_select_deep(self, queries: torch.Tensor, scores: torch.Tensor, rows: torch.Tensor, k: int, lam=0.5,
+                        n_cand=None, workspace: torch.Tensor = None, stream=None, return_objective: bool = False,
+                        stats: bool = False):
+        """mmr_select for 65..1,024 candidates per query and k up to their number (rfx_mmr_select_deep, bf16 /
+        f16 stores): the same arguments, rule and answer layout.  stats=True appends an int32 tensor [nq][2] —
+        per query the contenders summed over the steps and the exact dots taken (a view of the workspace)."""
+        import numpy as np
+        q = self._check_queries(queries)
+        nq = q.shape[0]
+        dev = q.device
+        if scores.shape != rows.shape or scores.dim() != 2 or scores.shape[0] != nq:
+            raise ValueError(f"candidates must be [nq={nq}][n_cand] scores and rows of equal shape")
+        if scores.dtype != torch.float32 or rows.dtype != torch.int64 or scores.device != dev or rows.device != dev:
+            raise ValueError("candidates must be (float32, int64) tensors on the queries' device")
+        cs, cr = scores.contiguous(), rows.contiguous()
+        n_max = cs.shape[1]
+        lam_a = np.ascontiguousarray(np.broadcast_to(np.asarray(lam, dtype=np.float32), (nq,)))
+        nc_a = None if n_cand is None else \
+            np.ascontiguousarray(np.broadcast_to(np.asarray(n_cand, dtype=np.int32), (nq,)))
+        need = self.mmr_deep_workspace_bytes(nq, n_max)
+        out_s = torch.empty((nq, k), dtype=torch.float32, device=dev)
+        out_r = torch.empty((nq, k), dtype=torch.int64, device=dev)
+        out_o = torch.empty((nq, k), dtype=torch.float32, device=dev) if return_objective else None
+        ws = workspace if workspace is not None and workspace.numel() >= need else \
+            torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            check(lib.rfx_mmr_select_deep(self.handle, ptr(q), nq, int(n_max), int(k), lam_a.ctypes.data,
+                                          nc_a.ctypes.data if nc_a is not None else None, ptr(cs), ptr(cr), ptr(out_s),
+                                          ptr(out_r), ptr(out_o) if out_o is not None else None, ptr(ws), ws.numel(),
+                                          stream_ptr(stream)))
+        res = (out_s, out_r) + ((out_o,) if return_objective else ())
+        return res + (ws[:8 * nq].view(torch.int32).view(nq, 2),) if stats else res
+
+    def search_mmr_deep(self, queries: torch.Tensor, k: int, fetch_k: int, lam=0.5, row_mask: torch.Tensor = None):
+        """The flat deep search at fetch_k (store.flat_search_deep), then the deep MMR selection of k of its
+        answer."""
+        from .store import flat_search_deep
+        if not (1 <= k <= fetch_k and 65 <= fetch_k <= 1024):
+            raise ValueError(f"need 1 <= k <= fetch_k and 65 <= fetch_k <= 1024, got k={k} fetch_k={fetch_k}")
+        s, r = flat_search_deep(self, queries, int(fetch_k), row_mask)
+        return self.mmr_select_deep(queries, s, r, int(k), lam=lam)
+
     # ---- distinct-document search (top-k documents, one best chunk each; DESIGN §4.17) --------------------
     def distinct_collapse(self, scores: torch.Tensor, rows: torch.Tensor, k: int, row_doc: torch.Tensor,
                           have: torch.Tensor = None, out=None, stream=None):
@@ -632,6 +680,14 @@ def deep_sampled_plan(rows: int, dim: int, dtype: str, nq: int, k: int):
     sampled-threshold deep search."""
     out = (ctypes.c_int * 6)()
     check(lib.rfx_deep_sampled_plan(int(rows), int(dim), _lib.DTYPE_CODES[dtype], int(nq), int(k), out))
+    return tuple(out)
+
+
+def mmr_deep_plan(nq: int, n_cand_max: int):
+    """Host only (rfx_mmr_deep_plan): (n_pad, tile pairs, queries per slice, slices, workspace bytes) of a deep
+    MMR selection."""
+    out = (ctypes.c_int64 * 5)()
+    check(lib.rfx_mmr_deep_plan(int(nq), int(n_cand_max), out))
     return tuple(out)
 
 

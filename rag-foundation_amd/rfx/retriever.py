@@ -162,6 +162,29 @@ def parse_hybrid_deep(hybrid, k: int):
     return alpha, fetch_k, rrf_c, k1, b
 
 
+def default_fetch_k_deep(k: int) -> int:
+    """Candidates a diversified question beyond 64 fetches when it names no fetch_k: min(1024, max(4k, 65))."""
+    return min(1024, max(4 * int(k), 65))
+
+
+def parse_diversity_deep(diversity, k: int):
+    """parse_diversity for a pool beyond 64: the same argument and the same rule for lambda, but
+    k <= fetch_k, 65 <= fetch_k <= 1024 and the default fetch_k is min(1024, max(4k, 65))."""
+    if diversity is None:
+        return None
+    fetch_k = diversity.get("fetch_k") if isinstance(diversity, dict) else None
+    rest = {n: v for n, v in diversity.items() if n != "fetch_k"} if isinstance(diversity, dict) else diversity
+    lam, _ = parse_diversity(rest, 1)
+    if fetch_k is not None and (isinstance(fetch_k, bool) or not isinstance(fetch_k, int)):
+        raise ValueError(f"diversity fetch_k={fetch_k!r} must be an integer")
+    fetch_k = default_fetch_k_deep(k) if fetch_k is None else int(fetch_k)
+    if not (k <= fetch_k and 65 <= fetch_k <= 1024):
+        raise ValueError(f"diversity fetch_k={fetch_k} must satisfy k={k} <= fetch_k and 65 <= fetch_k <= 1024")
+    return lam, fetch_k
+
+
+DIVERSITY_HYBRID_DEEP_ERROR = "diversity together with hybrid is not served beyond 64 candidates (k or fetch_k above 64)"
+
 _DISTINCT = "\x00distinct"  # tag of a store's distinct-document batchers (no filter_key starts with NUL)
 
 
@@ -856,7 +879,7 @@ class GpuRetriever:
         hits.sort(key=lambda h: h[:3])
         return [h[3] for h in hits[:k]]
 
-    def candidates(self, store_names, question, k, metadata_filter=None, hybrid=None):
+    def candidates(self, store_names, question, k, metadata_filter=None, hybrid=None, diversity=None):
         """The k best hits for 1 <= k <= 1024, rank order (score desc, store order, row asc): the candidate
         set of a stage behind the retriever (re-ranking, rank fusion, recall@100).  Up to 64 it is search();
         above, each named store answers with the deep search (LocalStore.search_deep: DeviceIndex.search_deep,
@@ -866,14 +889,22 @@ class GpuRetriever:
         hybrid: as search()'s; above 64 parse_hybrid_deep's (k <= fetch_k <= 1024, default k): each store answers
         with the reciprocal-rank fusion of its dense and its BM25 top fetch_k (flat_search_deep,
         LexIndex.search_deep, LexIndex.fuse_deep: DESIGN §4.21), Hit.score is the fused score and several stores
-        are merged by it.  ValueError (HYBRID_ERROR) on a sharded, IVF or f32 store."""
+        are merged by it.  ValueError (HYBRID_ERROR) on a sharded, IVF or f32 store.
+        diversity: as search()'s; with k above 64, or a fetch_k above 64 at any k, parse_diversity_deep's (k <=
+        fetch_k, 65 <= fetch_k <= 1024, default min(1024, max(4k, 65))): each store answers with the MMR selection
+        of k of its deep search's fetch_k best (DeviceIndex.search_mmr_deep), the answers are merged
+        by score and last_diversity is "store".  ValueError (DIVERSITY_ERROR) on a sharded, IVF or f32 store, and
+        together with hybrid (DIVERSITY_HYBRID_DEEP_ERROR)."""
         k = int(k)
         if not 1 <= k <= 1024:
             raise ValueError(f"k={k} out of range [1, 1024]")
-        if k <= 64:
-            if hybrid is not None:
-                return self.search(store_names, question, k, metadata_filter, hybrid=hybrid)
-            return self.search(store_names, question, k, metadata_filter)
+        fk = diversity.get("fetch_k") if isinstance(diversity, dict) else None
+        div = parse_diversity_deep(diversity, k) if k > 64 or (isinstance(fk, int) and fk > 64) else None
+        if div and hybrid is not None:
+            raise ValueError(DIVERSITY_HYBRID_DEEP_ERROR)
+        if k <= 64 and not div:
+            kw = {name: v for name, v in (("hybrid", hybrid), ("diversity", diversity)) if v is not None}
+            return self.search(store_names, question, k, metadata_filter, **kw)
         hyb = parse_hybrid_deep(hybrid, k)
         filt = filters.check_filter(metadata_filter)
         names = list(dict.fromkeys(store_names or []))
@@ -885,12 +916,16 @@ class GpuRetriever:
                 continue
             if hyb and not (_diversity_ok(st) and _deep_ok(st)):
                 raise ValueError(HYBRID_ERROR)
+            if div and not (_diversity_ok(st) and _deep_ok(st)):
+                raise ValueError(DIVERSITY_ERROR)
             if not _deep_ok(st):
                 raise ValueError(DEEP_ERROR)
             if st.index.rows == 0:
                 continue
             if hyb:
                 self.last_hybrid = "store"
+            if div:
+                self.last_diversity = "store"
 
             def run(st=st):
                 mask = st.row_mask(filt) if filt is not None else None
@@ -907,6 +942,9 @@ class GpuRetriever:
                         s, r = lex.fuse_deep(rd, rl, k, alpha, rrf_c=rrf_c)
                         return s[0].cpu().tolist(), r[0].cpu().tolist()
                     q = self.embedder(st.dim).embed_texts([question], st.dtype)
+                    if div:  # the deep search at fetch_k, then the selection of k of it (pick order)
+                        s, r = st.index.search_mmr_deep(q, k, div[1], lam=div[0], row_mask=mask)
+                        return s[0].cpu().tolist(), r[0].cpu().tolist()
                     if hasattr(st, "search_deep"):  # LocalStore: the lists of an IVF store, else the flat scan
                         sel = sum(n for _, n in st.mask_ranges(filt)) if mask is not None else None
                         s, r = st.search_deep(q, k, row_mask=mask, selected=sel)
