@@ -7,7 +7,7 @@ namespace rfx {
 int launch_scan_mfma6_dbg(const MfmaPlan& p, int mode, const void* X, int nrows, int dtype, const void* Qpad, int nq,
                           uint32_t* tau, float* cs, int* cr, hipStream_t st) {
   if (!p.ok || dtype != RFX_BF16) return -1;
-  if (mode == 0) return launch_scan_mfma6(p, X, nrows, 768, dtype, Qpad, nq, tau, cs, cr, st, nullptr);
+  if (mode == 0) return exact_scan(6)->launch(p, X, nrows, 768, dtype, Qpad, nq, tau, cs, cr, st, nullptr, nullptr, false);
   if (mode == 70 || mode == 71) {  // lane lists of 4 (k <= 4) with a 6- or 7-slot ring
     if (p.k_lane != 4) return -1;
     const int ntiles = (nrows + k6::kTM - 1) / k6::kTM;

@@ -1,4 +1,4 @@
-// k_mfma_common.h — device helpers shared by the MFMA scan kernels (k_scan_mfma3/4/5.h): MFMA
+// k_mfma_common.h — device helpers shared by the MFMA scan kernels (kernels 2, 3, 6, 8, 9, 10): MFMA
 // wrappers, orderable score keys, LDS-DMA / buffer-atomic inline asm, the shared pruning-bound
 // table reads and the per-lane top-k list fold.
 //
@@ -124,6 +124,45 @@ struct Acc4View {
   const v4f32x4 (&a)[4];
   __device__ __forceinline__ float operator[](int r) const { return a[r >> 2][r & 3]; }
 };
+
+// Register-resident sorted key list (kernels 2, 3): key takes its place, the last entry falls out.
+template <int KL>
+__device__ __forceinline__ void key_insert(uint64_t (&L)[KL], uint64_t key) {
+#pragma unroll
+  for (int i = 0; i < KL; ++i) {
+    const bool b = key > L[i];
+    const uint64_t t = L[i];
+    L[i] = b ? key : t;
+    key = b ? t : key;
+  }
+}
+
+// Kernels 6, 8, 9: threshold-table refreshes go out after the last stage of tiles 0, 1, 3, 7, 11, ... (the lists
+// start empty, so the first tiles take the slow insert path until the slot table's bound arrives;
+// then every 4 tiles: a staler bound sends more lanes into the insert path — kernel 5 ablations).
+__device__ __forceinline__ bool tau_refresh_tile(int it) { return it < 2 || (it & 3) == 3; }
+
+// Metadata filter (kernels 6, 8): row bit of the lane's value r after the epilogue's pair swap (fold ROWMAP 1,
+// bits pre-shifted by 8 * half): (r & 7) + 16 * (r >> 3).
+template <class V>
+__device__ __forceinline__ void mask_rowmap1(V& a, uint32_t bits) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+    if (!((bits >> ((r & 7) + 16 * (r >> 3))) & 1u)) a[r >> 2][r & 3] = __builtin_nanf("");
+}
+
+// Kernels 8, 9 (one-dimensional grid): block b -> (row range, query group).  paired: ranges is a multiple of 8,
+// and the groups of a range fall on one XCD.
+__device__ __forceinline__ void block_map(int b, int ranges, int groups, bool paired, int& range, int& grp) {
+  if (paired) {
+    const int xcd = b & 7, s = b >> 3;
+    range = (s / groups) * 8 + xcd;
+    grp = s % groups;
+  } else {
+    range = b % ranges;
+    grp = b / ranges;
+  }
+}
 
 // min over the first KL threshold slots of one query (LDS image [q][kTauW] u32, 48 B per query)
 template <int KL>

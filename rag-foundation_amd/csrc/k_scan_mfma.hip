@@ -281,7 +281,7 @@ static int mfma_k_lane(int k) {
   return -1;
 }
 
-MfmaPlan plan_scan_mfma(int64_t nrows, int D, int dtype, int64_t nq, int k) {
+static MfmaPlan plan_scan_mfma(int64_t nrows, int D, int dtype, int64_t nq, int k) {
   MfmaPlan p{};
   p.ok = (dtype == RFX_BF16 || dtype == RFX_F16) && D % kBK == 0 && nrows > 0;
   p.k_lane = mfma_k_lane(k);
@@ -357,12 +357,79 @@ int launch_scan_mfma_dbg(const MfmaPlan& p, int mode, const void* X, int nrows, 
   return 0;
 }
 
-int launch_scan_mfma(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                     float* cs, int* cr, hipStream_t st, const uint32_t* mask, const uint32_t* gate) {
+// (kernel 1 keeps no threshold table: tau and tau_zeroed are not used)
+static int launch_scan_mfma(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
+                            uint32_t*, float* cs, int* cr, hipStream_t st, const uint32_t* mask, const uint32_t* gate,
+                            bool) {
   if (!p.ok) return -1;
   if (dtype == RFX_BF16)
     return launch_mfma_bn<RFX_BF16>(p, (const uint16_t*)X, nrows, D, (const uint16_t*)Qpad, nq, cs, cr, st, mask, gate);
   return launch_mfma_bn<RFX_F16>(p, (const uint16_t*)X, nrows, D, (const uint16_t*)Qpad, nq, cs, cr, st, mask, gate);
+}
+
+// ---- the exact MFMA scans: the one place a kernel is registered -----------------------------------------
+// (each descriptor is a static of a host function beside its kernel: a namespace-scope constant would also be
+// emitted into the unit's device code, where the host functions it names do not exist)
+static const ExactScan& exact_scan_mfma1() {
+  static const ExactScan s{1, 2, plan_scan_mfma, [](const MfmaPlan&) -> size_t { return 0; }, launch_scan_mfma};
+  return s;
+}
+const ExactScan &exact_scan_mfma2(), &exact_scan_mfma3(), &exact_scan_mfma6(), &exact_scan_mfma8(), &exact_scan_mfma9();
+
+// In the order they are tried.  A kernel is tried for nq > min_nq, and, where two_pass_any is set, for every batch
+// that plans it as the two-pass scan's fallback (kernel 10 takes nq > 8; the batch is padded to the query group).
+// Kernel 9 plans f32 stores only, for nq > 16: as a fallback it also takes 9..16 questions, planned at two_pass_nq.
+struct Candidate {
+  const ExactScan* scan;
+  int min_nq;
+  bool two_pass_any;
+  int two_pass_nq;
+};
+constexpr int kExactScans = 6;
+static const Candidate* exact_scans() {
+  static const Candidate t[kExactScans] = {{&exact_scan_mfma6(), 128, true, 0},  {&exact_scan_mfma8(), 64, true, 0},
+                                           {&exact_scan_mfma3(), 64, false, 0},  {&exact_scan_mfma9(), 0, false, 17},
+                                           {&exact_scan_mfma2(), 128, false, 0}, {&exact_scan_mfma1(), 0, false, 0}};
+  return t;
+}
+
+const ExactScan* select_exact_scan(int64_t nrows, int D, int dtype, int64_t nq, int k, bool two_pass, MfmaPlan& mp) {
+  const Candidate* t = exact_scans();
+  for (int i = 0; i < kExactScans; ++i) {
+    const Candidate& c = t[i];
+    if (nq <= c.min_nq && !(two_pass && c.two_pass_any)) continue;
+    mp = c.scan->plan(nrows, D, dtype, two_pass ? std::max<int64_t>(nq, c.two_pass_nq) : nq, k);
+    if (mp.ok) return c.scan;
+  }
+  return nullptr;
+}
+
+const ExactScan* exact_scan(int kernel) {
+  const Candidate* t = exact_scans();
+  for (int i = 0; i < kExactScans; ++i)
+    if (t[i].scan->kernel == kernel) return t[i].scan;
+  return nullptr;
+}
+
+MfmaPlan plan_scan_ranges(bool ok, int qg, int tm, int lists_per_block, int max_groups, bool round8, int64_t nrows,
+                          int64_t nq, int k) {
+  MfmaPlan p{};
+  p.ok = ok && nrows > 0;
+  p.k_lane = k <= 4 ? 4 : (k <= 10 ? 10 : -1);
+  if (p.k_lane < 0) p.ok = false;
+  p.bn = qg;
+  p.q_blocks = (int)((nq + qg - 1) / qg);
+  p.nq_pad = (int64_t)p.q_blocks * qg;
+  if (p.q_blocks < 1 || p.q_blocks > max_groups) p.ok = false;
+  const int64_t ntiles = std::max<int64_t>((nrows + tm - 1) / tm, 1);
+  int64_t ranges = std::max<int64_t>(256 / std::max(p.q_blocks, 1), 1);
+  if (round8 && ranges >= 8) ranges = ranges / 8 * 8;
+  ranges = std::min<int64_t>(ranges, ntiles);
+  p.blocks = (int)ranges;
+  p.tiles_per_block = (int)((ntiles + ranges - 1) / ranges);
+  p.lists_per_block = lists_per_block;
+  p.n_lists = (int64_t)p.blocks * lists_per_block;
+  return p;
 }
 
 }  // namespace rfx

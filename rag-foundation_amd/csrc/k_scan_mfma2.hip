@@ -21,8 +21,7 @@
 //     value ever published is the KL-th best of some subset of rows, hence a lower bound of the
 //     global k-th best, so a stale read only filters less — results stay exact.
 // Algorithmic bytes per tile: 256 * D * 2 (corpus rows, read once).
-#include "rfx_device.h"
-#include "rfx_kernels.h"
+#include "k_mfma_common.h"
 
 namespace rfx {
 
@@ -41,18 +40,14 @@ __device__ __forceinline__ v2f32x16 mfma2(const uint4& a, const uint4& b, const 
                                                   0, 0, 0);
 }
 
-// float -> uint32 whose unsigned order is the float order (finite values and +-inf)
-__device__ __forceinline__ uint32_t ord32(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ uint64_t mkkey(float s, int row) {
-  return ((uint64_t)ord32(s) << 32) | (uint32_t)(~(uint32_t)row);
-}
+using mfc::key_insert;
+using mfc::max3f;
+using mfc::ord;
 
-// NaN-ignoring 3-way max as plain fmaxf (hipcc emits v_max3_f32 and pads the MFMA->VALU hazard an
-// inline-asm reader of an accumulator would not get).
-__device__ __forceinline__ float vmax3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+// (not cand_key of k_cand_keys.h, which folds -0 into +0: this key keeps the score's own bits)
+__device__ __forceinline__ uint64_t mkkey(float s, int row) {
+  return ((uint64_t)ord(s) << 32) | (uint32_t)(~(uint32_t)row);
+}
 
 constexpr int kB2M = 256, kB2N = 256, kB2K = 32;
 constexpr int kRowB = kB2K * 2;                    // 64 B per operand row per stage
@@ -62,17 +57,7 @@ constexpr int kRingB = 4;                          // queries (L2-resident): 3 s
 constexpr int kTauOff = (kRingA + kRingB) * kSlot;   // 144 KB
 constexpr int kLds = kTauOff + kB2N * 4;             // + 1 KB shared thresholds
 
-template <int KL>
-__device__ __forceinline__ void key_insert(uint64_t (&L)[KL], uint64_t key) {
-#pragma unroll
-  for (int i = 0; i < KL; ++i) {
-    const bool b = key > L[i];
-    const uint64_t t = L[i];
-    L[i] = b ? key : t;
-    key = b ? t : key;
-  }
-}
-
+// (the builtin, not mfc::glds: the compiler places M0 and sees the LDS write)
 __device__ __forceinline__ void glds16(const void* src, uint8_t* lds_dst) {
   __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
 }
@@ -243,27 +228,27 @@ __global__ __launch_bounds__(512) void scan_mfma2_kernel(const uint16_t* __restr
 #pragma unroll
           for (int m = 0; m < 4; ++m)
 #pragma unroll
-            for (int r = 0; r < 16; r += 2) mx = vmax3(mx, acc[m][n][r], acc[m][n][r + 1]);
+            for (int r = 0; r < 16; r += 2) mx = max3f(mx, acc[m][n][r], acc[m][n][r + 1]);
         } else {
 #pragma unroll
           for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int row = rbase + m * 32 + (r & 3) + 8 * (r >> 2);
-              mx = vmax3(mx, row < nrows ? acc[m][n][r] : -__builtin_inff(), -__builtin_inff());
+              mx = max3f(mx, row < nrows ? acc[m][n][r] : -__builtin_inff(), -__builtin_inff());
             }
         }
         const uint32_t shared_thr = *(const uint32_t*)(lds + tau_lds[n]);
         const uint32_t own = (uint32_t)(L[n][KL - 1] >> 32);
         const uint32_t thr = own > shared_thr ? own : shared_thr;
-        if (mx == mx && ord32(mx) >= thr) {
+        if (mx == mx && ord(mx) >= thr) {
 #pragma unroll
           for (int m = 0; m < 4; ++m)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int row = rbase + m * 32 + (r & 3) + 8 * (r >> 2);
               const float s = acc[m][n][r];
-              if (row < nrows && s == s && ord32(s) >= thr) {
+              if (row < nrows && s == s && ord(s) >= thr) {
                 const uint64_t key = mkkey(s, row);
                 if (key > L[n][KL - 1]) key_insert<KL>(L[n], key);
               }
@@ -301,7 +286,10 @@ __global__ __launch_bounds__(512) void scan_mfma2_kernel(const uint16_t* __restr
   }
 }
 
-MfmaPlan plan_scan_mfma2(int64_t nrows, int D, int dtype, int64_t nq, int k) {
+// thresholds [nq_pad] u32 + slack: 1 KB threshold DMA per group
+static size_t tau_bytes_mfma2(const MfmaPlan& p) { return (size_t)(p.nq_pad + 256) * sizeof(uint32_t); }
+
+static MfmaPlan plan_scan_mfma2(int64_t nrows, int D, int dtype, int64_t nq, int k) {
   MfmaPlan p{};
   p.ok = (dtype == RFX_BF16 || dtype == RFX_F16) && D % 64 == 0 && nrows > 0;
   p.k_lane = k <= 4 ? 4 : (k <= 8 ? 8 : (k <= 10 ? 10 : (k <= 16 ? 16 : -1)));
@@ -337,9 +325,9 @@ int launch_scan_mfma2_dbg(const MfmaPlan& p, int mode, const void* X, int nrows,
   return -1;
 }
 
-int launch_scan_mfma2(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask,
-                      const uint32_t* gate) {
+static int launch_scan_mfma2(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
+                             uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask,
+                             const uint32_t* gate, bool) {
   if (!p.ok) return -1;
   const int ntiles = (nrows + kB2M - 1) / kB2M;
   if (hipMemsetAsync(tau, 0, (size_t)p.nq_pad * sizeof(uint32_t), st) != hipSuccess) return -2;
@@ -356,6 +344,11 @@ int launch_scan_mfma2(const MfmaPlan& p, const void* X, int nrows, int D, int dt
   RFX_KL2(RFX_F16, 4) RFX_KL2(RFX_F16, 8) RFX_KL2(RFX_F16, 10) RFX_KL2(RFX_F16, 16)
 #undef RFX_KL2
   return -1;
+}
+
+const ExactScan& exact_scan_mfma2() {
+  static const ExactScan s{2, 2, plan_scan_mfma2, tau_bytes_mfma2, launch_scan_mfma2};
+  return s;
 }
 
 }  // namespace rfx

@@ -27,8 +27,7 @@
 // multiple of 128, so the ragged last tile needs no clamping or masking.
 // Algorithmic bytes per tile: 128 * D * 2.
 #pragma once
-#include "rfx_device.h"
-#include "rfx_kernels.h"
+#include "k_mfma_common.h"
 
 namespace rfx {
 namespace k3 {
@@ -47,13 +46,10 @@ __device__ __forceinline__ v3f32x16 mfma3(const uint4& a, const uint4& b, const 
                                                   0, 0, 0);
 }
 
-__device__ __forceinline__ uint32_t ord3(float f) {
-  const uint32_t b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-// NaN-ignoring 3-way max as plain fmaxf (hipcc emits v_max3_f32 and pads the MFMA->VALU hazard an
-// inline-asm reader of an accumulator would not get).
-__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+using mfc::glds;
+using mfc::key_insert;
+using mfc::max3f;
+using mfc::ord;
 
 constexpr int k3M = 128;        // rows per tile
 constexpr int k3QW = 32;        // queries per wave
@@ -64,23 +60,6 @@ constexpr int k3Ring = 8;                  // 7 stages (112 KB) in flight
 constexpr int k3GPW = k3Slot / 1024 / 4;   // LDS-DMA wave-instructions per wave per stage (4)
 constexpr int k3TauOff = k3Ring * k3Slot;  // 128 KB
 constexpr int k3Lds = k3TauOff + 1024;      // thresholds: 256 slots (128 used), one DMA wave-instruction
-
-// LDS-DMA (global_load_lds_dwordx4) issued from inline asm; M0 = wave-uniform LDS destination.
-__device__ __forceinline__ void glds_asm(const void* src, uint32_t lds_addr) {
-  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_addr)
-               : "memory", "m0");
-}
-
-template <int KL>
-__device__ __forceinline__ void key_insert3(uint64_t (&L)[KL], uint64_t key) {
-#pragma unroll
-  for (int i = 0; i < KL; ++i) {
-    const bool b = key > L[i];
-    const uint64_t t = L[i];
-    L[i] = b ? key : t;
-    key = b ? t : key;
-  }
-}
 
 template <int DT, int KL, int D>
 __global__ __launch_bounds__(256, 1) void scan_mfma3_kernel(const uint16_t* __restrict__ X, int nrows,
@@ -138,10 +117,10 @@ __global__ __launch_bounds__(256, 1) void scan_mfma3_kernel(const uint16_t* __re
     const uint16_t* tbase = X + (int64_t)(t0 + ti) * k3M * D + si * k3BK;
     const uint32_t dst = lds_base + (uint32_t)(slot * k3Slot) + (uint32_t)(w * 1024);
 #pragma unroll
-    for (int u = 0; u < k3GPW; ++u) glds_asm(tbase + laneoff[u], __builtin_amdgcn_readfirstlane(dst + u * 4096));
+    for (int u = 0; u < k3GPW; ++u) glds(tbase + laneoff[u], __builtin_amdgcn_readfirstlane(dst + u * 4096));
   };
   // shared thresholds of this query group -> LDS (every wave, 64 lanes x 16 B = 1 KB; identical data)
-  auto issue_tau = [&]() { glds_asm(tau + qg + lane * 4, __builtin_amdgcn_readfirstlane(lds_base + k3TauOff)); };
+  auto issue_tau = [&]() { glds(tau + qg + lane * 4, __builtin_amdgcn_readfirstlane(lds_base + k3TauOff)); };
 
   uint64_t L[KL];
 #pragma unroll
@@ -237,8 +216,8 @@ __global__ __launch_bounds__(256, 1) void scan_mfma3_kernel(const uint16_t* __re
           const float s = acc[m][r];
           if (s >= thr) {  // NaN (tombstoned rows, rows past the end) never passes
             const int row = rbase + m * 32 + (r & 3) + 8 * (r >> 2);
-            const uint64_t key = ((uint64_t)ord3(s) << 32) | (uint32_t)(~(uint32_t)row);
-            if (key > L[KL - 1]) key_insert3<KL>(L, key);
+            const uint64_t key = ((uint64_t)ord(s) << 32) | (uint32_t)(~(uint32_t)row);
+            if (key > L[KL - 1]) key_insert<KL>(L, key);
           }
         }
       const uint32_t pub = (uint32_t)(L[KL - 1] >> 32);

@@ -63,20 +63,6 @@ constexpr int lds_bytes() { return list_off<RING>() + kWaves * KL * 64 * 8; }
 static_assert(lds_bytes<10, 6>() <= 163840 && lds_bytes<4, 7>() <= 163840, "LDS budget");
 static_assert(kSlot / 1024 == kWaves * kGPW && kTauGPW == 2, "DMA pieces per wave");
 
-// Threshold-table refreshes go out after the last stage of tiles 0, 1, 3, 7, 11, ... (the lists
-// start empty, so the first tiles take the slow insert path until the slot table's bound arrives;
-// then every 4 tiles: a staler bound sends more lanes into the insert path — kernel 5 ablations).
-__device__ __forceinline__ bool tau_refresh_tile(int it) { return it < 2 || (it & 3) == 3; }
-
-// Metadata filter: row bit of the lane's value r after the epilogue's pair swap (fold ROWMAP 1,
-// bits pre-shifted by 8 * half): (r & 7) + 16 * (r >> 3).
-template <class V>
-__device__ __forceinline__ void mask_rowmap1(V& a, uint32_t bits) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-    if (!((bits >> ((r & 7) + 16 * (r >> 3))) & 1u)) a[r >> 2][r & 3] = __builtin_nanf("");
-}
-
 // Debug-build ablations of the first tile's fold (MODE 64 / 256 below).  fold_nopub: the list insert
 // of mfc::fold (ROWMAP 1) without publishing the list's best to the slot table.  fold_first: the
 // lane's list is empty at tile 0, so each of the 16 values goes straight to its final position

@@ -60,29 +60,7 @@ constexpr int lds_bytes() { return kListOff + kWaves * KL * 64 * 8; }
 static_assert(lds_bytes<10>() <= 163840, "LDS budget");
 static_assert(kSlot / 1024 == kWaves * kGPW && kTauGPW == 1, "DMA pieces per wave");
 
-__device__ __forceinline__ bool tau_refresh_tile(int it) { return it < 2 || (it & 3) == 3; }
-
-// Metadata filter on the pair-swapped 32-row layout (kernel 6's): value r of the lane is row
-// (r & 7) + 16 (r >> 3) of its 32-row half, bits pre-shifted by 8 * half.
-template <class V>
-__device__ __forceinline__ void mask_rowmap1(V& a, uint32_t bits) {
-#pragma unroll
-  for (int r = 0; r < 16; ++r)
-    if (!((bits >> ((r & 7) + 16 * (r >> 3))) & 1u)) a[r >> 2][r & 3] = __builtin_nanf("");
-}
-
 constexpr int kModeMask = 2097152;
-
-__device__ __forceinline__ void block_map(int b, int ranges, int groups, bool paired, int& range, int& grp) {
-  if (paired) {
-    const int xcd = b & 7, s = b >> 3;
-    range = (s / groups) * 8 + xcd;
-    grp = s % groups;
-  } else {
-    range = b % ranges;
-    grp = b / ranges;
-  }
-}
 
 template <int DT, int KL, int D, int MODE = 0>
 __global__ __launch_bounds__(512, 1) void scan_mfma8_kernel(const uint16_t* __restrict__ X, const uint16_t* __restrict__ Qp,

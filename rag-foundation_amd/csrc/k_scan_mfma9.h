@@ -51,8 +51,6 @@ constexpr int lds_bytes() { return kListOff + kWaves * 2 * KL * 64 * 8; }
 static_assert(lds_bytes<10>() <= 163840, "LDS budget");
 static_assert(kGPW == 4 && kTauGPW == 2, "DMA pieces per wave");
 
-__device__ __forceinline__ bool tau_refresh_tile(int it) { return it < 2 || (it & 3) == 3; }
-
 template <class V>
 __device__ __forceinline__ void mask_rowmap2(V& a, uint64_t bits) {
 #pragma unroll
@@ -61,17 +59,6 @@ __device__ __forceinline__ void mask_rowmap2(V& a, uint64_t bits) {
 }
 
 constexpr int kModeMask = 2097152;
-
-__device__ __forceinline__ void block_map(int b, int ranges, int groups, bool paired, int& range, int& grp) {
-  if (paired) {
-    const int xcd = b & 7, s = b >> 3;
-    range = (s / groups) * 8 + xcd;
-    grp = s % groups;
-  } else {
-    range = b % ranges;
-    grp = b / ranges;
-  }
-}
 
 __device__ __forceinline__ v4f32x4 mfma4(float a, float b, const v4f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);

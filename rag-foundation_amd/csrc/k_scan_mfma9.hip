@@ -9,34 +9,18 @@ int launch_f32_768(int kl, dim3 grid, hipStream_t st, const float* X, const floa
                    const uint32_t* mask, int mask_words, const uint32_t* gate);
 }  // namespace k9
 
-size_t tau_bytes_mfma9(const MfmaPlan& p) { return (size_t)p.nq_pad * k9::kTauW * sizeof(uint32_t); }
+static size_t tau_bytes_mfma9(const MfmaPlan& p) { return (size_t)p.nq_pad * k9::kTauW * sizeof(uint32_t); }
 
-// f32 stores, 16 < nq: 128 queries per workgroup, G = ceil(nq / 128) query groups × R row ranges,
-// R·G ≈ 256 (R a multiple of 8: the groups of a range share an XCD).  Below 17 queries the VALU
+// f32 stores, 16 < nq: 128 queries per workgroup, the groups of a range on one XCD.  Below 17 queries the VALU
 // scan's 8-query slices cost less than a 128-query MFMA pass (the kernel computes all 128 columns).
-MfmaPlan plan_scan_mfma9(int64_t nrows, int D, int dtype, int64_t nq, int k) {
-  MfmaPlan p{};
-  p.ok = dtype == RFX_F32 && D == 768 && nrows > 0 && nq > 16;
-  p.k_lane = k <= 4 ? 4 : (k <= 10 ? 10 : -1);
-  if (p.k_lane < 0) p.ok = false;
-  p.bn = k9::kQG;
-  p.q_blocks = (int)((nq + k9::kQG - 1) / k9::kQG);
-  p.nq_pad = (int64_t)p.q_blocks * k9::kQG;
-  if (p.q_blocks < 1 || p.q_blocks > 32) p.ok = false;
-  const int64_t ntiles = std::max<int64_t>((nrows + k9::kTM - 1) / k9::kTM, 1);
-  int64_t ranges = std::max<int64_t>(256 / std::max(p.q_blocks, 1), 1);
-  if (ranges >= 8) ranges = ranges / 8 * 8;
-  ranges = std::min<int64_t>(ranges, ntiles);
-  p.blocks = (int)ranges;
-  p.tiles_per_block = (int)((ntiles + ranges - 1) / ranges);
-  p.lists_per_block = k9::kListsPerBlock;
-  p.n_lists = (int64_t)p.blocks * k9::kListsPerBlock;
-  return p;
+static MfmaPlan plan_scan_mfma9(int64_t nrows, int D, int dtype, int64_t nq, int k) {
+  return plan_scan_ranges(dtype == RFX_F32 && D == 768 && nq > 16, k9::kQG, k9::kTM, k9::kListsPerBlock, 32, true,
+                          nrows, nq, k);
 }
 
-int launch_scan_mfma9(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask, const uint32_t* gate,
-                      bool tau_zeroed) {
+static int launch_scan_mfma9(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
+                             uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask,
+                             const uint32_t* gate, bool tau_zeroed) {
   static_assert(k9::kTauW == kFallbackTauW, "screen_queries_kernel zeroes this table for the gated fallback");
   if (!p.ok || D != 768 || dtype != RFX_F32) return -1;
   const int ntiles = (nrows + k9::kTM - 1) / k9::kTM;
@@ -45,6 +29,12 @@ int launch_scan_mfma9(const MfmaPlan& p, const void* X, int nrows, int D, int dt
   dim3 grid(p.blocks * p.q_blocks);
   return k9::launch_f32_768(p.k_lane, grid, st, (const float*)X, (const float*)Qpad, nq, ntiles, p.blocks,
                             p.q_blocks, paired, tau, cs, cr, p.n_lists, mask, (nrows + 31) / 32, gate);
+}
+
+// f32 stores: batched scan on v_mfma_f32_16x16x4_f32
+const ExactScan& exact_scan_mfma9() {
+  static const ExactScan s{9, 4, plan_scan_mfma9, tau_bytes_mfma9, launch_scan_mfma9};
+  return s;
 }
 
 }  // namespace rfx

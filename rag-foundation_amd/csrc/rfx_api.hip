@@ -453,6 +453,7 @@ struct SearchLayout {
                      // VALU plan vp)
   rfx::ValuPlan vp;
   rfx::MfmaPlan mp;
+  const rfx::ExactScan* scan;  // the exact MFMA scan of plan mp (kernel, or fbk under 10 / 12); nullptr: the VALU scan
   int64_t n_cand;    // candidates per query
   size_t q_off, q_bytes, tau_off, cs_off, cr_off, total;
   // kernel 10 (the two-pass scan): the exact plan above (kernel fbk, regions q/tau/cs/cr) is its
@@ -502,45 +503,13 @@ int make_layout(const Index& ix, int64_t nq, int k, SearchLayout& L, bool search
     if (!wsp.ok) wsp = wsmax;
   }
   const bool wide = wsmax.ok;
-  if (nq > 8 && !(wide && k > 16)) {
-    if (nq > 128 || (two_pass && nq > 8)) {
-      L.mp = rfx::plan_scan_mfma6(ix.rows, ix.dim, ix.dtype, nq, k);
-      if (L.mp.ok) L.kernel = 6;
-    }
-    if (L.kernel == 0 && (nq > 64 || two_pass)) {  // d = 1024: kernel 8 (k-split wave pairs)
-      L.mp = rfx::plan_scan_mfma8(ix.rows, ix.dim, ix.dtype, nq, k);
-      if (L.mp.ok) L.kernel = 8;
-    }
-    if (L.kernel == 0 && nq > 64) {
-      L.mp = rfx::plan_scan_mfma3(ix.rows, ix.dim, ix.dtype, nq, k);
-      if (L.mp.ok) L.kernel = 3;
-    }
-    if (L.kernel == 0 && ix.dtype == RFX_F32) {
-      // (kernel 9 plans nq > 16; as the two-pass scan's fallback it also takes 9..16 questions, padded to 128)
-      L.mp = rfx::plan_scan_mfma9(ix.rows, ix.dim, ix.dtype, two_pass ? std::max<int64_t>(nq, 17) : nq, k);
-      if (L.mp.ok) L.kernel = 9;
-    }
-    if (L.kernel == 0 && nq > 128) {
-      L.mp = rfx::plan_scan_mfma2(ix.rows, ix.dim, ix.dtype, nq, k);
-      if (L.mp.ok) L.kernel = 2;
-    }
-    if (L.kernel == 0) {
-      L.mp = rfx::plan_scan_mfma(ix.rows, ix.dim, ix.dtype, nq, k);
-      if (L.mp.ok) L.kernel = 1;
-    }
-  }
+  if (nq > 8 && !(wide && k > 16)) L.scan = rfx::select_exact_scan(ix.rows, ix.dim, ix.dtype, nq, k, two_pass, L.mp);
   size_t tau_bytes = 0;
-  if (L.kernel) {
+  if (L.scan) {
+    L.kernel = L.scan->kernel;
     L.n_cand = L.mp.n_lists * L.mp.k_lane;
-    L.q_bytes = (size_t)L.mp.nq_pad * ix.dim * (L.kernel == 9 ? 4 : 2);
-    if (L.kernel == 6)  // (the debug build's kernel-5 ablations use the same [nq_pad][16] table)
-      tau_bytes = rfx::tau_bytes_mfma6(L.mp);
-    else if (L.kernel == 8)
-      tau_bytes = rfx::tau_bytes_mfma8(L.mp);
-    else if (L.kernel == 9)
-      tau_bytes = rfx::tau_bytes_mfma9(L.mp);
-    else if (L.kernel >= 2)
-      tau_bytes = (size_t)(L.mp.nq_pad + 256) * 4;  // + slack: 1 KB threshold DMA per group
+    L.q_bytes = (size_t)L.mp.nq_pad * ix.dim * L.scan->q_esz;
+    tau_bytes = L.scan->tau_bytes(L.mp);
   } else {
     if (!L.vp.ok) return fail(RFX_EUNSUPPORTED, "no scan kernel for dim=%d dtype=%d k=%d", ix.dim, ix.dtype, k);
     L.n_cand = (int64_t)L.vp.n_lists * L.vp.k_slot;
@@ -663,16 +632,11 @@ int scan_into(Index& ix, const SearchLayout& L, const void* queries, int64_t nq,
     const void* qpad = queries;
     if (nq != L.mp.nq_pad || ((uintptr_t)queries & 15)) {
       qpad = ws + L.q_off;
-      rfx::launch_pad_queries(queries, nq, L.mp.nq_pad, ix.dim, L.kernel == 9 ? 4 : 2, (void*)qpad, st);
+      rfx::launch_pad_queries(queries, nq, L.mp.nq_pad, ix.dim, L.scan->q_esz, (void*)qpad, st);
     }
     uint32_t* tau = (uint32_t*)(ws + L.tau_off);
-    const int rc =
-        L.kernel == 6 ? rfx::launch_scan_mfma6(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs, cr, st, mask)
-        : L.kernel == 8 ? rfx::launch_scan_mfma8(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs, cr, st, mask)
-        : L.kernel == 9 ? rfx::launch_scan_mfma9(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs, cr, st, mask)
-        : L.kernel == 3 ? rfx::launch_scan_mfma3(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs, cr, st, mask)
-        : L.kernel == 2 ? rfx::launch_scan_mfma2(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs, cr, st, mask)
-                        : rfx::launch_scan_mfma(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, cs, cr, st, mask);
+    const int rc = L.scan->launch(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs, cr, st, mask,
+                                  nullptr, false);
     if (rc != 0) return fail(RFX_EUNSUPPORTED, "MFMA scan launch rejected (%d)", rc);
   } else {
     float* qf = (float*)(ws + L.q_off);
@@ -755,18 +719,9 @@ int screen_search(Index& ix, const SearchLayout& L, const void* queries, int64_t
     return RFX_OK;
   }
   // gated exact pass (no work unless the select kernel set the gate)
-  const int rc = L.fbk == 1 ? rfx::launch_scan_mfma(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, cs, cr, st,
-                                                    mask, gate)
-                 : L.fbk == 2 ? rfx::launch_scan_mfma2(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs,
-                                                       cr, st, mask, gate)
-                 : L.fbk == 3 ? rfx::launch_scan_mfma3(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs,
-                                                       cr, st, mask, gate)
-                 : L.fbk == 6 ? rfx::launch_scan_mfma6(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs,
-                                                     cr, st, mask, gate, true)
-                 : L.fbk == 8 ? rfx::launch_scan_mfma8(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs,
-                                                       cr, st, mask, gate, true)
-                              : rfx::launch_scan_mfma9(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs,
-                                                       cr, st, mask, gate, true);
+  // (tau_zeroed: the query quantiser cleared kernel 6 / 8 / 9's table above; kernels 2 / 3 ignore it)
+  const int rc = L.scan->launch(L.mp, ix.data, (int)ix.rows, ix.dim, ix.dtype, qpad, (int)nq, tau, cs, cr, st, mask,
+                                gate, true);
   if (rc != 0) return fail(RFX_EUNSUPPORTED, "fallback scan launch rejected (%d)", rc);
   // (the fallback's final top-k re-scored by the two-pass rule: the same bits as the select's answer)
   if (rfx::launch_topk_merge_lists(cs, cr, 0, nq, L.n_cand, L.mp.k_lane, k, row_offset, out_rec ? nullptr : out_s,
@@ -1584,16 +1539,16 @@ int rfx_dbg_scan_variant(rfx_index_t h, const void* queries_d, int64_t nq, int k
   rfx::launch_pad_queries(queries_d, nq, L.mp.nq_pad, ix->dim, 2, qpad, st);
   int rc2;
   if (mode >= 20000000)  // headline kernel (k_scan_mfma6.h) ablations: mode 20000000 + MODE
-    rc2 = rfx::launch_scan_mfma6_dbg(rfx::plan_scan_mfma6(ix->rows, ix->dim, ix->dtype, nq, k), mode - 20000000, ix->data,
+    rc2 = rfx::launch_scan_mfma6_dbg(rfx::exact_scan(6)->plan(ix->rows, ix->dim, ix->dtype, nq, k), mode - 20000000, ix->data,
                                      (int)ix->rows, ix->dtype, qpad, (int)nq, (uint32_t*)((uint8_t*)ws_d + L.tau_off), cs, cr, st);
   else if (mode >= 10 && mode < 20)  // 256x256 kernel ablations: mode 10 + MODE
-    rc2 = rfx::launch_scan_mfma2_dbg(rfx::plan_scan_mfma2(ix->rows, ix->dim, ix->dtype, nq, k), mode - 10, ix->data,
+    rc2 = rfx::launch_scan_mfma2_dbg(rfx::exact_scan(2)->plan(ix->rows, ix->dim, ix->dtype, nq, k), mode - 10, ix->data,
                                      (int)ix->rows, ix->dim, qpad, (int)nq, (uint32_t*)((uint8_t*)ws_d + L.tau_off),
                                      cs, cr, st);
   else if (mode == 3)  // the production kernel for this plan
     return scan_into(*ix, L, queries_d, nq, cs, cr, (uint8_t*)ws_d, st);
   else
-    rc2 = rfx::launch_scan_mfma_dbg(rfx::plan_scan_mfma(ix->rows, ix->dim, ix->dtype, nq, k), mode, ix->data,
+    rc2 = rfx::launch_scan_mfma_dbg(rfx::exact_scan(1)->plan(ix->rows, ix->dim, ix->dtype, nq, k), mode, ix->data,
                                     (int)ix->rows, ix->dim, qpad, (int)nq, cs, cr, st);
   if (rc2 != 0) return fail(RFX_EUNSUPPORTED, "variant unsupported for this plan");
   RFX_HIP(hipGetLastError());

@@ -89,45 +89,33 @@ struct MfmaPlan {
   int64_t nq_pad;
   bool ok;
 };
-MfmaPlan plan_scan_mfma(int64_t nrows, int D, int dtype, int64_t nq, int k);
-// gate (kernels 1, 2, 3; optional): a device word; the kernel returns at once when it is clear (the exact pass of
-// the wide two-pass scan at k 11..16, plan 12).  Kernels 2 / 3 clear their bounds by a memset either way.
-int launch_scan_mfma(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad,
-                     int nq, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr,
-                     const uint32_t* gate = nullptr);
+// One exact MFMA scan (kernels 1, 2, 3, 6, 8, 9; each defined beside its kernel, listed in k_scan_mfma.hip).
+struct ExactScan {
+  int kernel;  // the number rfx_scan_plan / rfx_search_plan report
+  int q_esz;   // bytes per element of the padded queries [nq_pad][D]
+  MfmaPlan (*plan)(int64_t nrows, int D, int dtype, int64_t nq, int k);
+  size_t (*tau_bytes)(const MfmaPlan& p);  // the threshold table at `tau` (0: kernel 1 has none)
+  // gate (optional): a device word; the kernel returns at once when it is clear (the exact pass of a two-pass
+  // scan runs only when the screen's select kernel asked for it).  tau_zeroed: the caller has cleared the
+  // table (kernels 6, 8, 9: no memset launch then; kernels 2 / 3 clear their bounds by a memset either way).
+  int (*launch)(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
+                uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask, const uint32_t* gate,
+                bool tau_zeroed);
+};
+// The scan of a batch of nq > 8 questions and its plan (mp), or nullptr (mp.ok false): the VALU scan's.
+// two_pass: the plan is the gated fallback of kernel 10, which takes 6 / 8 / 9 whatever nq.
+const ExactScan* select_exact_scan(int64_t nrows, int D, int dtype, int64_t nq, int k, bool two_pass, MfmaPlan& mp);
+const ExactScan* exact_scan(int kernel);  // by number (the debug build's variants)
+// kernels 6, 8, 9: G = ceil(nq / qg) query groups (at most max_groups) x R row ranges of tm-row tiles, R·G ≈ 256
+// (round8: R a multiple of 8, so the groups of a range share an XCD); block b of a group scans tiles b, b + R, ...
+MfmaPlan plan_scan_ranges(bool ok, int qg, int tm, int lists_per_block, int max_groups, bool round8, int64_t nrows,
+                          int64_t nq, int k);
 int launch_scan_mfma_dbg(const MfmaPlan& p, int mode, const void* X, int nrows, int D, const void* Qpad, int nq,
                          float* cs, int* cr, hipStream_t st);
-MfmaPlan plan_scan_mfma2(int64_t nrows, int D, int dtype, int64_t nq, int k);
-int launch_scan_mfma2(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr,
-                      const uint32_t* gate = nullptr);
 int launch_scan_mfma2_dbg(const MfmaPlan& p, int mode, const void* X, int nrows, int D, const void* Qpad, int nq,
                           uint32_t* tau, float* cs, int* cr, hipStream_t st);
-MfmaPlan plan_scan_mfma3(int64_t nrows, int D, int dtype, int64_t nq, int k);
-int launch_scan_mfma3(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr,
-                      const uint32_t* gate = nullptr);
-size_t tau_bytes_mfma6(const MfmaPlan& p);
-MfmaPlan plan_scan_mfma6(int64_t nrows, int D, int dtype, int64_t nq, int k);
-// gate (optional): a device word; the launch does nothing unless it is non-zero (the exact pass of
-// the two-pass scan runs only when the screen's select kernel asked for it)
-int launch_scan_mfma6(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr,
-                      const uint32_t* gate = nullptr, bool tau_zeroed = false);
 int launch_scan_mfma6_dbg(const MfmaPlan& p, int mode, const void* X, int nrows, int dtype, const void* Qpad, int nq,
                           uint32_t* tau, float* cs, int* cr, hipStream_t st);
-size_t tau_bytes_mfma8(const MfmaPlan& p);
-MfmaPlan plan_scan_mfma8(int64_t nrows, int D, int dtype, int64_t nq, int k);
-int launch_scan_mfma8(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr,
-                      const uint32_t* gate = nullptr, bool tau_zeroed = false);
-// f32 stores (kernel 9): batched scan on v_mfma_f32_16x16x4_f32 for 16 < nq
-size_t tau_bytes_mfma9(const MfmaPlan& p);
-MfmaPlan plan_scan_mfma9(int64_t nrows, int D, int dtype, int64_t nq, int k);
-// gate / tau_zeroed: as kernel 6 (the exact pass of the two-pass scan of an f32 store)
-int launch_scan_mfma9(const MfmaPlan& p, const void* X, int nrows, int D, int dtype, const void* Qpad, int nq,
-                      uint32_t* tau, float* cs, int* cr, hipStream_t st, const uint32_t* mask = nullptr,
-                      const uint32_t* gate = nullptr, bool tau_zeroed = false);
 void launch_pad_queries(const void* Q, int64_t nq, int64_t nq_pad, int D, int esz, void* out,
                         hipStream_t st);
 

@@ -398,6 +398,29 @@ def test_mfma_matches_valu_path(rfx):
         assert abs(s1[qi, ki] - s2[qi, ki]) <= 2 * TIE
 
 
+# 993 rows: 32 tiles of 32 rows, the fewest with which the wide form (8-wave, d 768) has its 64 lists; a ragged
+# last tile for the 64-row kernels 8 and 9.  9 questions: the smallest batch of a two-pass scan, which kernels 6 / 8
+# pad to a query group and kernel 9 plans as 17.
+@pytest.mark.parametrize("dtype,dim,nq,k,kern", [("bf16", 768, 9, 10, 10),    # fallback: kernel 6
+                                                 ("f16", 1024, 9, 10, 10),    # kernel 8
+                                                 ("f32", 768, 9, 10, 10),     # kernel 9
+                                                 ("bf16", 768, 65, 16, 12)])  # the wide form over kernel 3
+def test_forced_two_pass_fallback_equals_unscreened(rfx, dtype, dim, nq, k, kern):
+    """enable_screen(2) sends the batch through the gated exact pass: the rows and score bits of the unscreened search."""
+    rindex, _ = rfx
+    ix = rindex.DeviceIndex(dim, dtype)
+    ix.add_synthetic(7, 993)
+    q = rindex.synth_rows(8, 0, nq, dim, dtype)
+    s0, r0 = ix.search(q, k)
+    ix.enable_screen(2)
+    assert ix.search_plan(nq, k) == kern
+    ws = torch.empty(ix.workspace_bytes(nq, k), dtype=torch.uint8, device="cuda")
+    s1, r1 = ix.search(q, k, workspace=ws)
+    assert ix.screen_diag(nq, k, ws)[1], "the fallback did not run"
+    assert torch.equal(r0, r1) and torch.equal(s0.view(torch.int32), s1.view(torch.int32))
+    ix.close()
+
+
 def test_self_retrieval_property(rfx):
     """Size-independent property: a stored row used as the query ranks itself first (score 1)."""
     rindex, _ = rfx
