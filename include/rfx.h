@@ -259,7 +259,7 @@ int rfx_distinct_collapse(rfx_index_t h, const int32_t* row_doc_d, int64_t n_row
                           const float* cand_scores_d, const int64_t* cand_rows_d, const int32_t* have_d /* may be NULL */,
                           float* out_scores_d, int64_t* out_rows_d, int32_t* out_docs_d, int32_t* out_n_d,
                           int32_t* out_done_d, void* stream);
-/* Deep search: the exact top-k of the live rows for k in 65..1024, the depth that a re-ranking
+/* Deep search (f32 stores: §4.23): the exact top-k of the live rows for k in 65..1024, the depth that a re-ranking
  * stage, rank fusion at depth 100+ or a recall@100 evaluation reads behind the retrieval slice of ask_stream
  * (gemini_rag.py:517-551); every other rfx_search* stops at k = 64.  Same score rule and order as every
  * rfx_search* (fl32 of the f64 dot of the stored values; score desc, row asc — equal scores go to the lower row,
@@ -268,7 +268,8 @@ int rfx_distinct_collapse(rfx_index_t h, const int32_t* row_doc_d, int64_t n_row
  * (rows + 31) / 32 words.  Outputs [nq][k] (device); positions past the selected live rows hold (-inf, -1).
  * Two launches (scan, merge), stream-ordered.  RFX_EINVAL before anything is enqueued: k outside 65..1024, nq
  * outside 0..1024, null or unaligned pointers, a workspace under rfx_search_deep_workspace_bytes.
- * RFX_EUNSUPPORTED: an f32 store, a union view, dim not a multiple of 64 or above 1024. */
+ * RFX_EUNSUPPORTED: a union view, dim not a multiple of 64 or above 1024.  bf16, f16 and f32 stores are served,
+ * an f32 store by a scan of its own on the f32 MFMA (k_deep_f32.h) behind the same arguments and workspace. */
 int rfx_search_deep_workspace_bytes(rfx_index_t h, int64_t nq, int k, size_t* out_bytes);
 int rfx_search_deep(rfx_index_t h, const void* queries_d, int64_t nq, int k, const uint32_t* row_mask_d /* may be NULL */,
                     float* out_scores_d, int64_t* out_rows_d, void* ws_d, size_t ws_bytes, void* stream);
@@ -276,7 +277,8 @@ int rfx_search_deep(rfx_index_t h, const void* queries_d, int64_t nq, int k, con
  * KB, questions per workgroup}: range i holds rows [i * rows_per_range, (i + 1) * rows_per_range), the last one
  * runs to the end of the store; a range holds at least 4 * KB rows unless there is only one; KB = k rounded up to
  * 128 / 256 / 512 / 1024; a workgroup's candidate buffers take questions * 2 * KB * 8 bytes of LDS.  Same
- * errors as rfx_search_deep. */
+ * errors as rfx_search_deep, and RFX_EUNSUPPORTED for an f32 dtype: the query describes the bf16 / f16 scan (an
+ * f32 store is split by the same numbers). */
 int rfx_deep_plan(int64_t rows, int dim, int dtype, int64_t nq, int k, int* out /* [4] */);
 /* Deep search, sampled threshold: rfx_search_deep's answer — same arguments, score rule, order,
  * padding, argument checks and error codes — by another route: the k-th best score of a strided sample of the

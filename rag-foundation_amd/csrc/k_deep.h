@@ -40,4 +40,8 @@ int launch_deep_search(const DeepPlan& p, const void* X, int64_t nrows, int D, i
                        const uint32_t* mask, uint64_t* ws, float* out_s, int64_t* out_r, hipStream_t st,
                        const int* nq_dev = nullptr);
 
+// The merge alone, for a scan that filled ws itself (k_deep_f32.h): any dtype the score rule serves.
+void launch_deep_merge(const DeepPlan& p, const void* X, int64_t nrows, int D, int dtype, const void* Q, int64_t nq, int k,
+                       const uint64_t* ws, float* out_s, int64_t* out_r, hipStream_t st, const int* nq_dev = nullptr);
+
 }  // namespace rfx

@@ -1,8 +1,9 @@
 // k_deep.hip — the deep search kernels (k_deep.h): scan with threshold + LDS buffer + periodic sort, and the
-// per-question merge with the f64 re-score.  Keys, slot claim, sort and cut: k_cand_keys.h.  gfx950 only.
+// per-question merge with the f64 re-score.  Keys, slot claim, sort and cut: k_cand_keys.h; the buffers and the
+// meeting, shared with the f32 scan: k_deep_buf.h.  gfx950 only.
 #include "k_deep.h"
 
-#include "k_cand_keys.h"
+#include "k_deep_buf.h"
 #include "k_mfma_common.h"
 #include "k_scan_valu.h"  // rescore_dot: the score rule's f64 dot
 
@@ -10,33 +11,6 @@ namespace rfx {
 namespace {
 
 using mfc::v4f32x4;
-
-constexpr int kDeepQSlots = 16;  // threshold / count slots of a workgroup (questions per workgroup <= 16)
-
-// LDS of a workgroup: nqg buffers of 2 * KB keys, then the thresholds (keys; 0 = none yet) and the fills.
-struct DeepBuf {
-  uint64_t* buf;
-  uint64_t* tau;
-  int* cnt;
-  int KB;
-  __device__ __forceinline__ DeepBuf(uint64_t* lds, int nqg, int kb)
-      : buf(lds), tau(lds + (size_t)nqg * 2 * kb), cnt((int*)(lds + (size_t)nqg * 2 * kb + kDeepQSlots)), KB(kb) {}
-};
-size_t deep_lds_bytes(int nqg, int kb) { return (size_t)nqg * 2 * kb * 8 + kDeepQSlots * 8 + kDeepQSlots * 4; }
-
-// Workgroup-wide meeting after a round of appends.  Every buffer that holds more than `lim` keys is sorted, its
-// KB best stay and the KB-th becomes its threshold (lim = -1: every buffer, the final cut).  Returns the buffers
-// it cut (uniform).  Nothing may be appended between the entry and the return.
-__device__ __forceinline__ uint32_t deep_compact(const DeepBuf& B, int nqg, int lim) {
-  const int N = 2 * B.KB;
-  __syncthreads();  // the round's appends are in
-  uint32_t need = 0;
-  for (int q = 0; q < nqg; ++q) need |= (B.cnt[q] > lim ? 1u : 0u) << q;
-  __syncthreads();  // every thread has read the fills before anyone appends again
-  if (!need) return 0;
-  cand_cut(B.buf, N, B.KB, need, B.cnt, B.tau);
-  return need;
-}
 
 // ---- scan ---------------------------------------------------------------------------------------------------
 // A fragments of the 16-row tile at r0 (NDS * 64 columns at most, nds * 64 in use) and the tile's live bits:
@@ -231,20 +205,19 @@ int launch_scan_dt(const DeepPlan& p, const void* X, int nrows, int D, const voi
 
 }  // namespace
 
+void launch_deep_merge(const DeepPlan& p, const void* X, int64_t nrows, int D, int dtype, const void* Q, int64_t nq, int k,
+                       const uint64_t* ws, float* out_s, int64_t* out_r, hipStream_t st, const int* nq_dev) {
+  hipLaunchKernelGGL(deep_merge_kernel, dim3((unsigned)nq), dim3(kDeepThreads), deep_lds_bytes(1, p.kb), st, ws, p.ranges, p.kb,
+                     k, X, (int)nrows, D, dtype, Q, out_s, out_r, nq_dev);
+}
+
 int launch_deep_search(const DeepPlan& p, const void* X, int64_t nrows, int D, int dtype, const void* Q, int64_t nq, int k,
                        const uint32_t* mask, uint64_t* ws, float* out_s, int64_t* out_r, hipStream_t st, const int* nq_dev) {
-  if (dtype != RFX_BF16 && dtype != RFX_F16) return -1;
-  if (D < 64 || D > kDeepMaxDim || D % 64 != 0) return -1;
-  if (nq < 1 || nq > kDeepMaxNq || k < kDeepMinK || k > p.kb || nrows < 0 || nrows > 0x7fffffffll - 1) return -1;
-  if (p.ranges < 1 || p.check_rounds < 2 || p.check_rounds % 2 != 0 || 2 * p.kb < p.kb + p.check_rounds * kDeepRound ||
-      p.q_per_wg > kDeepQSlots || (int64_t)(p.ranges - 1) * p.rows_per_range > nrows)
-    return -1;
+  if ((dtype != RFX_BF16 && dtype != RFX_F16) || !deep_launch_ok(p, nrows, D, nq, k)) return -1;
   const int rc = dtype == RFX_BF16 ? launch_scan_dt<RFX_BF16>(p, X, (int)nrows, D, Q, (int)nq, mask, ws, nq_dev, st)
                                    : launch_scan_dt<RFX_F16>(p, X, (int)nrows, D, Q, (int)nq, mask, ws, nq_dev, st);
   if (rc) return rc;
-  const size_t lds = deep_lds_bytes(1, p.kb);
-  hipLaunchKernelGGL(deep_merge_kernel, dim3((unsigned)nq), dim3(kDeepThreads), lds, st, ws, p.ranges, p.kb, k, X, (int)nrows,
-                     D, dtype, Q, out_s, out_r, nq_dev);
+  launch_deep_merge(p, X, nrows, D, dtype, Q, nq, k, ws, out_s, out_r, st, nq_dev);
   return 0;
 }
 

@@ -220,7 +220,7 @@ class DeviceIndex:
 
     def search_deep(self, queries: torch.Tensor, k: int, row_mask: torch.Tensor = None, workspace: torch.Tensor = None,
                     stream=None):
-        """Exact top-k rows per query for k in 65..1024 on a bf16 / f16 store (rfx_search_deep): (scores f32
+        """Exact top-k rows per query for k in 65..1024 on a bf16 / f16 / f32 store (rfx_search_deep): (scores f32
         [nq][k], rows int64 [nq][k]) on the device, padded with (-inf, -1) past the selected live rows."""
         q = self._check_queries(queries)
         nq = q.shape[0]

@@ -215,15 +215,25 @@ def _search_diverse(index, q, items, div_at, row_mask=None):
     return s.cpu(), r.cpu()
 
 
-DEEP_ERROR = "candidates beyond 64 need flat bf16 / f16 single-device stores"
+DEEP_ERROR = "candidates beyond 64 need flat single-device stores"
 
 
 def _deep_ok(st) -> bool:
-    """A flat bf16 / f16 store on one device: its index runs the deep search (DeviceIndex.search_deep).  With
-    RFX_IVF_DEEP=1 an IVF store of such rows too (LocalStore.search_deep: through its lists)."""
+    """A flat store on one device: its index runs the deep search (DeviceIndex.search_deep; f32 rows: DESIGN
+    §4.23).  With RFX_IVF_DEEP=1 an IVF store of bf16 / f16 rows too (LocalStore.search_deep: through its lists,
+    DESIGN §4.19)."""
     kind = getattr(st, "spec", {}).get("kind", "flat")
-    return hasattr(st.index, "search_deep") and st.dtype in ("bf16", "f16") and \
-        (kind == "flat" or (kind == "ivf" and ivf_deep_mode() and hasattr(st, "search_deep")))
+    if not hasattr(st.index, "search_deep"):
+        return False
+    if kind == "flat":
+        return st.dtype in ("bf16", "f16", "f32")
+    return kind == "ivf" and st.dtype in ("bf16", "f16") and ivf_deep_mode() and hasattr(st, "search_deep")
+
+
+def _diversity_deep_ok(st) -> bool:
+    """A flat bf16 / f16 store on one device: the deep MMR selection (DeviceIndex.search_mmr_deep)
+    has no f32 kernel."""
+    return _diversity_ok(st) and hasattr(st.index, "search_deep") and st.dtype in ("bf16", "f16")
 
 
 class _StoreAnswer(tuple):
@@ -884,12 +894,12 @@ class GpuRetriever:
         set of a stage behind the retriever (re-ranking, rank fusion, recall@100).  Up to 64 it is search();
         above, each named store answers with the deep search (LocalStore.search_deep: DeviceIndex.search_deep,
         exact, or the lists of an IVF store under RFX_IVF_DEEP=1) under its own lock and row numbering, and the
-        answers are merged.  ValueError (DEEP_ERROR) on a sharded or f32 store, and on an IVF store without
-        RFX_IVF_DEEP=1.
+        answers are merged.  A flat f32 store is served too.  ValueError (DEEP_ERROR) on a sharded
+        store, on an IVF store without RFX_IVF_DEEP=1 and on an IVF store of f32 rows.
         hybrid: as search()'s; above 64 parse_hybrid_deep's (k <= fetch_k <= 1024, default k): each store answers
         with the reciprocal-rank fusion of its dense and its BM25 top fetch_k (flat_search_deep,
         LexIndex.search_deep, LexIndex.fuse_deep: DESIGN §4.21), Hit.score is the fused score and several stores
-        are merged by it.  ValueError (HYBRID_ERROR) on a sharded, IVF or f32 store.
+        are merged by it.  ValueError (HYBRID_ERROR) on a sharded or IVF store.
         diversity: as search()'s; with k above 64, or a fetch_k above 64 at any k, parse_diversity_deep's (k <=
         fetch_k, 65 <= fetch_k <= 1024, default min(1024, max(4k, 65))): each store answers with the MMR selection
         of k of its deep search's fetch_k best (DeviceIndex.search_mmr_deep), the answers are merged
@@ -916,7 +926,7 @@ class GpuRetriever:
                 continue
             if hyb and not (_diversity_ok(st) and _deep_ok(st)):
                 raise ValueError(HYBRID_ERROR)
-            if div and not (_diversity_ok(st) and _deep_ok(st)):
+            if div and not _diversity_deep_ok(st):
                 raise ValueError(DIVERSITY_ERROR)
             if not _deep_ok(st):
                 raise ValueError(DEEP_ERROR)

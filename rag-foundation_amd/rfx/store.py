@@ -168,8 +168,9 @@ def deep_sampled_mode() -> bool:
 
 
 def flat_search_deep(index, queries, k, row_mask=None):
-    """The flat deep search of `index` by the route RFX_DEEP_SAMPLED names."""
-    if deep_sampled_mode():
+    """The flat deep search of `index` by the route RFX_DEEP_SAMPLED names; an f32 index takes search_deep
+    whatever it says (the sampled-threshold scan is bf16 / f16)."""
+    if deep_sampled_mode() and index.dtype != "f32":
         return index.search_deep_sampled(queries, k, row_mask=row_mask)
     return index.search_deep(queries, k, row_mask=row_mask)
 
